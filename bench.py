@@ -15,7 +15,7 @@ graph (weak scaling at N > 1: N*1e5 rows, p 0.01/N).
 the graph is the build's R-MAT stand-in of LiveJournal's size and skew (csrc/er_gen.h rmat_edge: scale
 22 = 4.19M vertices, edge factor 10, (a,b,c) = (0.5,0.2,0.2), seed 1; about 82M arcs, maxDeg about 26K),
 the wide sweep (uint16 colours); under torchrun the graph is vertex-partitioned (strong scaling). The run
-converges, so the one-GPU line also carries the full --mcmcgpu run from the initial colouring:
+converges, so the one-GPU --full line also carries the full --mcmcgpu run from the initial colouring:
 sweeps-to-zero-conflict and its wall time.
 `--semantics ref` (one GPU): the same sweep with the reference GPU colorer's own semantics
 (--mcmcgpu-ref: balance-dynamic proposal, per-vertex cuRAND XORWOW, conflicts counted as edges);
@@ -23,18 +23,29 @@ its CPU leg times the oracle's restatement of those semantics.
 
 A step is one sweep: all n vertices resampled. Inputs are resident in HBM before the timed region;
 the timed region is K back-to-back sweeps (one hipGraph at N = 1) bracketed by barrier + synchronize,
-max over ranks. Prints ONE JSON line (rank 0). Besides the driver contract fields it carries
+max over ranks. Prints ONE JSON line (rank 0).
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what the headline figure needs and no
+more: graph generation, W warm-up sweeps, the K timed sweeps, the result line (the driver contract
+fields, `ms_per_step`, and the roofline / dense / wide_inc records priced from the device counters of
+the timed sweeps themselves). `--dump-outputs DIR` then writes the colouring the timed sweeps left
+(what a caller of the path receives from mcmc_get_coloring) as DIR/coloring.npy, float32, one colour
+per vertex: graph, seed and glibc stream are fixed by the arguments, so two builds can be compared
+vertex for vertex. Everything that takes runs of its own sits behind `--full` (the --no-* options
+drop single legs of it):
   roofline     : the sweep kernel's bytes per launch in its layout (B_fmt; the
                  reference-layout B_alg beside it) / its average duration, measured with hipEvents on
                  the kernel's own stream, against the 8 TB/s HBM peak; traffic = PMC HBM bytes per
-                 launch from the committed rocprofv3 summary (profiles/pmc_summary.json)
+                 launch from the committed rocprofv3 summary (profiles/pmc_summary.json). (In every
+                 run; --full adds the tiled sweep's device-counted scan bytes, 3 sweeps of their own,
+                 and the scan / full-scan comparison runs.)
   refstruct    : the reference CUDA path's per-sweep structure re-expressed in HIP (the stand-in for
                  "the reference CUDA path's vertex-updates/sec", which cannot run on MI355X)
   cpu_baseline : the oracle (faithful single-thread restatement of --mcmccpu, kind "port") on this
                  host, a bounded number of sweeps
 For c3 the CPU leg runs on `--simulate 0.1 -n 100000` (C3's mean degree, 1e4) and the refstruct leg on a
 2e6-row graph of the same degree (full occupancy at thread-per-vertex): C3's own uint32 CSR (400 GB)
-cannot exist on the host or one GPU. Every single-GPU line also carries `convergence`: the reference
+cannot exist on the host or one GPU. Every single-GPU --full line also carries `convergence`: the reference
 loop run from the initial colouring (sweeps-to-zero-conflict, or not converged at 251 + final Cviol +
 trajectory).
 """
@@ -328,6 +339,14 @@ def main() -> int:
     ap.add_argument("--prob", type=float, default=0.01)
     ap.add_argument("--ncol", type=int, default=16)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, everything that takes runs of its own: the CPU baseline, "
+                         "the refstruct leg, the reference-loop run (convergence, C5 violators), the scan / "
+                         "full-scan comparisons and the tiled sweep's scan statistics; the --no-* options "
+                         "drop single legs of it. Without --full none of them runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the colouring they left (what mcmc_get_coloring returns "
+                         "to a caller, one colour per vertex) as DIR/coloring.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-refstruct", action="store_true", help="skip the refstruct (reference-structure) leg")
     ap.add_argument("--no-convergence", action="store_true", help="skip the reference-loop run (sweeps-to-zero-conflict)")
@@ -346,6 +365,8 @@ def main() -> int:
                     help="K > 1: time one rank's share of configs[3] (rows [0, n/K) of the C3 graph) on this GPU, "
                          "as a plain sweep and as a world-K rank with the exchange left out (rank_share)")
     a = ap.parse_args()
+    if not a.full:   # a plain run: set-up, warm-up, the timed steps, the result line
+        a.no_cpu_baseline = a.no_refstruct = a.no_convergence = a.no_full_scan = True
     if a.rank_share > 1:
         print(json.dumps(rank_share(a)), flush=True)
         return 0
@@ -511,6 +532,12 @@ def main() -> int:
         dist.all_reduce(w, op=dist.ReduceOp.MAX)
         wall = float(w.item())
 
+    if a.dump_outputs and rank == 0:
+        # what the timed path hands its caller: the colouring after the last timed sweep (graph, seed
+        # and glibc stream are fixed by the arguments, the sweep is bit-reproducible)
+        Path(a.dump_outputs).mkdir(parents=True, exist_ok=True)
+        np.save(Path(a.dump_outputs) / "coloring.npy", (col if dist is None else drv).coloring().astype(np.float32))
+
     n, m = g.nNodes, g.nEdges
     if dist is not None and a.config == "c3":   # per-rank graphs hold their rows' arcs only
         import torch
@@ -605,7 +632,7 @@ def main() -> int:
                                 "what": ("the tiled early-exit scan (MCMC_DENSE=0)" if env == "MCMC_DENSE" else
                                          "every arc scanned (MCMC_FULL_SCAN=1)")}
                 cf.close()
-    if not ref and variant == "tiled":
+    if a.full and not ref and variant == "tiled":
         # The tiled sweep stops scanning a row once its occupancy mask holds every colour (the
         # result cannot change; MCMC_FULL_SCAN=1 scans every arc): the bytes one launch moves are
         # counted on the device (mcmc_set_scan_stats, 3 sweeps outside the timed region) -- id quads,

@@ -8,6 +8,6 @@ trap "kill $HB" EXIT
 timeout -k 10 400 python -u -m pytest -x -q --timeout 150 --timeout-method thread -m gpu tests/test_dense.py > $OUT/t.log 2>&1
 rc=$?; tail -1 $OUT/t.log; [ $rc -eq 0 ] || exit $rc
 for cfg in c3 c2 c5; do
-  timeout -k 10 400 python -u bench.py --config $cfg > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err || { tail -5 $OUT/bench_$cfg.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --config $cfg > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err || { tail -5 $OUT/bench_$cfg.err; exit 1; }
   echo "$cfg: $(python3 -c "import json;d=json.loads(open('$OUT/bench_$cfg.json').read().splitlines()[-1]);c=d.get('convergence') or {};print(d['value'], d['ms_per_step'], d['roofline']['kernel_ms'], c.get('loop_ms'), c.get('rebuild_ms'), (d.get('cpu_baseline') or {}).get('value'))")"
 done

@@ -9,9 +9,9 @@ Q="--no-refstruct --no-convergence --no-full-scan --no-cpu-baseline"
 bash scripts/gpu_prof.sh ${1:-r04}_c3 $Q || exit $?
 bash scripts/gpu_prof.sh ${1:-r04}_c2 --config c2 $Q || exit $?
 bash scripts/gpu_prof.sh ${1:-r04}_c5 --config c5 $Q || exit $?
-timeout -k 10 900 python3 -u bench.py --steps 20 --warmup 5 > $O/bench_c3_driver.log 2>&1 || exit $?
+timeout -k 10 900 python3 -u bench.py --full --steps 20 --warmup 5 > $O/bench_c3_driver.log 2>&1 || exit $?
 echo "c3 $(grep '^{' $O/bench_c3_driver.log | cut -c1-400)"
-timeout -k 10 600 python3 -u bench.py --config c2 > $O/bench_c2.log 2>&1 || exit $?
+timeout -k 10 600 python3 -u bench.py --full --config c2 > $O/bench_c2.log 2>&1 || exit $?
 echo "c2 $(grep '^{' $O/bench_c2.log | cut -c1-300)"
-timeout -k 10 600 python3 -u bench.py --config c5 > $O/bench_c5.log 2>&1 || exit $?
+timeout -k 10 600 python3 -u bench.py --full --config c5 > $O/bench_c5.log 2>&1 || exit $?
 echo "c5 $(grep '^{' $O/bench_c5.log | cut -c1-300)"

@@ -16,6 +16,6 @@ rc=$?; echo "pytest rc=$rc"; tail -4 $OUT/pytest_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -2 $OUT/smoke.log
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 900 python -u bench.py > $OUT/bench_default.log 2>&1
+timeout -k 10 900 python -u bench.py --full > $OUT/bench_default.log 2>&1
 rc=$?; echo "bench rc=$rc"; tail -1 $OUT/bench_default.log | cut -c1-3000
 exit $rc
