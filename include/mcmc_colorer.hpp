@@ -352,6 +352,115 @@ private:
     int lastRepetition{0};
 };
 
+// ---- batched independent chains (mcmc_chains_*, csrc/chains.hip; no reference counterpart) ------
+// `chains` colourings of one graph as one batch: chain r is ColoringMCMC::run(r) (engine seed
+// seed + r), except that every chain draws its CDF-overflow colours from its OWN copy of the
+// process glibc window as it stands at run() -- run(r + 1) continues the stream run(r) left. The
+// process window is left where chain 0's ended. save(r) writes what ColoringMCMC::run(r) writes.
+template <typename nodeW, typename edgeW>
+class ColoringMCMCChains {
+public:
+    ColoringMCMCChains(Graph<nodeW, edgeW>* inGraph_d, GPURandHandle* randStates, ColoringMCMCParams params,
+                       uint32_t chains)
+        : graph(inGraph_d), seed(randStates->seed), param(params), R(chains) {}
+    ~ColoringMCMCChains() { mcmc_chains_destroy(ctx); }
+
+    void run() {
+        mcmc_chains_destroy(ctx);
+        ctx = nullptr;
+        mcmc_params p{};
+        p.nCol = param.nCol;
+        p.epsilon = param.epsilon;
+        p.lambda = param.lambda;
+        p.ratioFreezed = param.ratioFreezed;
+        p.numColorRatio = param.numColorRatio;
+        p.maxRip = param.maxRip;
+        p.tabooIteration = param.tabooIteration;
+        p.tailcut = param.tailcut;
+        p.seed = seed;
+        const uint64_t* ro = nullptr;
+        const uint32_t* ci = nullptr;
+        if (mcmc_graph_device_ptrs(graph->handle(), &ro, &ci) != MCMC_OK)   // a generated graph: the chains scan a CSR
+            MCMC_CHECK(mcmc_graph_materialize_csr(const_cast<mcmc_graph*>(graph->handle())));
+        MCMC_CHECK(mcmc_chains_create(graph->handle(), &p, R, &ctx));
+        MCMC_CHECK(mcmc_chains_set_tailcut_repair(ctx, param.tailcutRepair));
+        std::vector<uint32_t> w((size_t)R * 31);
+        for (uint32_t r = 0; r < R; r++) std::memcpy(&w[(size_t)r * 31], mcmc::glibc_global().w, 31 * sizeof(uint32_t));
+        MCMC_CHECK(mcmc_chains_set_glibc_windows(ctx, w.data()));
+        stats.assign(R, mcmc_run_stats{});
+        MCMC_CHECK(mcmc_chains_run(ctx, 0, stats.data()));
+        MCMC_CHECK(mcmc_chains_get_glibc_windows(ctx, w.data()));
+        std::memcpy(mcmc::glibc_global().w, w.data(), 31 * sizeof(uint32_t));
+    }
+
+    uint32_t chains() const { return R; }
+    const mcmc_run_stats& getStats(uint32_t r) const { return stats.at(r); }
+    std::vector<uint32_t> getColoring(uint32_t r) const {
+        std::vector<uint32_t> c(graph->getNNodes());
+        MCMC_CHECK(mcmc_chains_get_coloring(ctx, r, c.data()));
+        return c;
+    }
+    std::vector<uint64_t> getTrajectory(uint32_t r) const {
+        std::vector<uint64_t> t(stats.at(r).trajLen);
+        uint64_t len = 0;
+        MCMC_CHECK(mcmc_chains_get_trajectory(ctx, r, t.data(), t.size(), &len));
+        return t;
+    }
+
+    // <directory>.log and <directory>-colors.txt of chain r, in ColoringMCMC::save's layout.
+    void save(uint32_t r, const std::string& directory) const {
+        const std::vector<uint32_t> coloring = getColoring(r);
+        const std::vector<uint64_t> trajectory = getTrajectory(r);
+        const mcmc_run_stats& st = stats.at(r);
+        std::ofstream out(directory + ".log");
+        const uint32_t nCol = param.nCol;
+        out << "MCMC Colorer - GPU (MI355X) version - Report" << std::endl;
+        out << "-------------------------------------------" << std::endl;
+        out << "GRAPH INFO" << std::endl;
+        out << "Nodes: " << graph->getNNodes() << " - Edges: " << graph->getNEdges() << std::endl;
+        out << "Max deg: " << graph->getMaxNodeDeg() << " - Min deg: " << graph->getMinNodeDeg()
+            << " - Avg deg: " << graph->getMeanNodeDeg() << std::endl;
+        out << "Edge probability (for randomly generated graphs): " << graph->prob << std::endl;
+        out << "Seed: " << seed + r << std::endl;
+        out << "-------------------------------------------" << std::endl;
+        out << "EXECUTION INFO" << std::endl;
+        out << "Repetition: " << r << std::endl;
+        out << "Execution time: " << st.loopMs / 1000.0 << std::endl;   // the batch's loop
+        out << "Iteration performed: " << st.iter << std::endl;
+        out << "Max iteration reached: " << (st.maxIterReached ? "yes" : "no") << std::endl;
+        out << "-------------------------------------------" << std::endl;
+        out << "Color histogram:" << std::endl;
+        std::vector<size_t> hist(nCol, 0);
+        for (uint32_t c : coloring) hist[c]++;
+        size_t used = 0;
+        for (size_t i = 0; i < nCol; i++) { out << i << ": " << hist[i] << std::endl; if (hist[i]) used++; }
+        out << "Number of colors: " << nCol << " - Used colors: " << used << std::endl;
+        out << "Color ratio: " << param.numColorRatio << std::endl;
+        float mean = 0;
+        for (size_t h : hist) mean += (float)h;
+        mean /= (float)nCol;
+        float var = 0;
+        for (size_t h : hist) var += ((h - mean) * (h - mean));
+        var /= (float)nCol;
+        out << "Average number of nodes for each color: " << mean << std::endl;
+        out << "Variance: " << var << std::endl;
+        out << "StD: " << std::sqrt(var) << std::endl;
+        out << "Conflicts per sweep (C violations):";
+        for (uint64_t x : trajectory) out << " " << x;
+        out << std::endl;
+        std::ofstream cf(directory + "-colors.txt");
+        for (size_t i = 0; i < coloring.size(); i++) cf << i << " " << coloring[i] << "\n";
+    }
+
+private:
+    Graph<nodeW, edgeW>* graph;
+    uint32_t seed;
+    ColoringMCMCParams param;
+    uint32_t R;
+    mcmc_chains* ctx{nullptr};
+    std::vector<mcmc_run_stats> stats;
+};
+
 // ---- ColoringMCMC_CPU's class surface (graph_coloring/coloringMCMC_CPU.h:15-31) ----------------
 // The reference's --mcmccpu colorer, run by the same HIP sweep as ColoringMCMC (its semantics ARE
 // the CPU colorer's: bit-identical colouring, iteration count and glibc stream). Kept: the ctor

@@ -248,6 +248,42 @@ typedef struct mcmc_ctx_info {
 int mcmc_get_info(mcmc_ctx* c, mcmc_ctx_info* out);
 void mcmc_destroy(mcmc_ctx* c);
 
+/* ---- batched independent chains (csrc/chains.hip; no reference counterpart: the reference's
+ *      --repet N runs its colourings one after another, main.cu:170-202) ---------------------------
+ * R chains of one graph as one batch, one wave lane per chain. Chain r is, bit for bit,
+ * ColoringMCMC_CPU(g, params, seed + r).run() (the semantics of mcmc_run): its own engine
+ * std::default_random_engine(seed + r) (its own initDraws), its own sweep count, trajectory, iter,
+ * maxIterReached, finalViol and glibcDraws. A sweep that finds Cviol <= z for a chain is discarded
+ * for that chain (no colour change, no glibc draw).
+ * glibc streams: every chain draws its CDF-overflow colours (coloringMCMC_CPU.cpp:518) from ITS OWN
+ * 31-word window, events of one sweep in ascending vertex order. This differs from --repet /
+ * ColoringMCMC::run(i), where repetition i + 1 continues the one process stream where repetition i
+ * stopped: chain r equals repetition r only when both start at the same window (always, while no
+ * overflow occurs -- ~1e-7 per draw at the default epsilon).
+ * Supported: 2 <= nCol <= 64 (one 64-bit occupancy mask per lane), 1 <= R <= 1024, a graph with a
+ * whole device CSR (mcmc_graph_upload, _simulate, _rmat, or mcmc_graph_materialize_csr after
+ * mcmc_graph_er_fast); anything else is MCMC_E_ARG. Device memory: 2 n 64 ceil(R / 64) bytes of
+ * colours, 4 times half of that again for the taboo counters when tabooIteration > 0, 16 n
+ * ceil(R / 64) bytes of overflow records, the trajectories; MCMC_E_NOMEM with the byte counts when
+ * it does not fit. The context borrows `g`. */
+typedef struct mcmc_chains mcmc_chains;
+/* params.seed is chain 0's seed. Draws every chain's initial colouring (mcmc_init_coloring's). */
+int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mcmc_chains** out);
+/* windows[R][31]; default: every chain at srand(1) with no draws (mcmc_set_glibc_window's default).
+ * mcmc_chains_get_glibc_windows returns them advanced by each chain's glibcDraws. */
+int mcmc_chains_set_glibc_windows(mcmc_chains* c, const uint32_t* windows /* [R][31] */);
+int mcmc_chains_get_glibc_windows(mcmc_chains* c, uint32_t* windows /* [R][31] */);
+/* The tail-cut repair of mcmc_set_tailcut_repair is not available to chains: max_passes > 0 is
+ * MCMC_E_ARG (0 is accepted). */
+int mcmc_chains_set_tailcut_repair(mcmc_chains* c, uint32_t max_passes);
+/* Every chain's run() loop; each stops at its own sweep. max_sweeps > 0: at most that many sweeps
+ * (chains still running then report iter = sweeps, finalViol = ~0, as mcmc_run; a later call
+ * continues). stats[R] (may be NULL): per chain, loopMs = the batch's device time (hipEvent). */
+int mcmc_chains_run(mcmc_chains* c, uint32_t max_sweeps, mcmc_run_stats* stats /* R */);
+int mcmc_chains_get_coloring(mcmc_chains* c, uint32_t r, uint32_t* out /* n */);
+int mcmc_chains_get_trajectory(mcmc_chains* c, uint32_t r, uint64_t* out, uint64_t cap, uint64_t* len);
+void mcmc_chains_destroy(mcmc_chains* c);
+
 /* ---- measurement baseline (not part of the colouring path) ----------------------------------
  * "refstruct" (SURVEY.md §8d): the reference CUDA path's per-sweep structure re-expressed in HIP --
  * thread-per-vertex serial row walks in 64-thread blocks, an n*nCol byte checker reset per sweep, two

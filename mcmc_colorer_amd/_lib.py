@@ -64,6 +64,14 @@ SIGNATURES: dict[str, tuple] = {
     "mcmc_cdf_walk": (c_uint32, [_u32p, c_uint32, c_uint32, c_float, c_float, c_float]),
     "mcmc_refstruct_bench": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, POINTER(c_double), _u64p]),
     "mcmc_destroy": (None, [c_void_p]),
+    "mcmc_chains_create": (c_int, [c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
+    "mcmc_chains_set_glibc_windows": (c_int, [c_void_p, _u32p]),
+    "mcmc_chains_get_glibc_windows": (c_int, [c_void_p, _u32p]),
+    "mcmc_chains_set_tailcut_repair": (c_int, [c_void_p, c_uint32]),
+    "mcmc_chains_run": (c_int, [c_void_p, c_uint32, c_void_p]),
+    "mcmc_chains_get_coloring": (c_int, [c_void_p, c_uint32, _u32p]),
+    "mcmc_chains_get_trajectory": (c_int, [c_void_p, c_uint32, _u64p, c_uint64, _u64p]),
+    "mcmc_chains_destroy": (None, [c_void_p]),
     "mcmc_part_plan_rows": (c_int, [c_uint32, c_uint32, _u32p]),
     "mcmc_part_plan": (c_int, [c_void_p, c_uint32, c_int, _u32p]),
     "mcmc_part_plan_csr": (c_int, [_u64p, c_uint32, c_uint32, _u32p]),

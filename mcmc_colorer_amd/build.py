@@ -25,7 +25,10 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"--offload-arch={ARCH}",
           f"-I{ROOT / 'include'}", f"-I{CSRC}", "-Wall", "-Wno-unused-function"]
 LIB_SOURCES = ["mcmc_sweep.hip", "graph.hip", "tiled_layout.hip", "refstruct.hip", "tailcut.hip", "refmode.hip", "rmat.hip",
-               "greedyff.hip", "luby.hip", "multi.hip"]
+               "greedyff.hip", "luby.hip", "multi.hip", "chains.hip"]
+# per-source flags: chains.hip is compiled without the packed fp32 instructions (its CDF walk is
+# scalar fp32 per lane by construction; the packed forms bring nothing and are kept out)
+EXTRA = {"chains.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # RCCL (multi.hip: the native multi-GPU path); torch's bundled librccl.so.1 satisfies the same soname
 # when torch is loaded first
 LINK = ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]
@@ -53,7 +56,7 @@ def build_lib(force: bool = False) -> Path:
         o = BUILD / (src + ".o")
         objs.append(o)
         if force or _stale(o, [s] + headers):
-            jobs.append([HIPCC, *COMMON, "-c", s, "-o", o])
+            jobs.append([HIPCC, *COMMON, *EXTRA.get(src, []), "-c", s, "-o", o])
     if jobs:
         with ThreadPoolExecutor(max_workers=min(4, len(jobs))) as ex:
             list(ex.map(_run, jobs))

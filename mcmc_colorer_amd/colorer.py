@@ -354,6 +354,75 @@ class ColoringMCMC:
             pass
 
 
+class ColoringMCMCChains:
+    """``chains`` independent colourings of one graph as one batch (csrc/chains.hip): one wave lane
+    per chain, the adjacency read once for all of them.
+
+    Chain r is, bit for bit, ``ColoringMCMC.run(r)`` with engine seed ``seed + r`` -- except that
+    every chain draws its CDF-overflow colours from its own glibc window (``glibc``: one GlibcRand
+    whose position every chain starts at, or a list of ``chains`` of them; advanced in place by
+    ``run()``), where ``ColoringMCMC.run(i + 1)`` continues the stream ``run(i)`` left. 2 <= nCol <= 64,
+    1 <= chains <= 1024, a graph with a device CSR; no tail-cut repair."""
+
+    def __init__(self, graph: Graph, params: ColoringMCMCParams, seed: int, chains: int, glibc=None):
+        if params.nCol == 0:
+            params = ColoringMCMCParams(**{**params.__dict__, "nCol": default_ncol(graph, params)})
+        self.graph, self.param, self.seed, self.chains = graph, params, seed, int(chains)
+        self._h = ctypes.c_void_p()
+        if getattr(graph, "generated", False):
+            check(lib().mcmc_graph_materialize_csr(graph.handle))
+        self._cparams = params.to_c(seed)
+        check(lib().mcmc_chains_create(graph.handle, ctypes.byref(self._cparams), self.chains, ctypes.byref(self._h)))
+        check(lib().mcmc_chains_set_tailcut_repair(self._h, int(params.tailcutRepair)))
+        if glibc is None:
+            glibc = GlibcRand(1)
+        self.glibc = [glibc] * self.chains if isinstance(glibc, GlibcRand) else list(glibc)
+        self._stats: list[MCMCRunStats] = []
+
+    def run(self, max_sweeps: int = 0) -> list[MCMCRunStats]:
+        w = np.ascontiguousarray(np.stack([g.window for g in self.glibc]), dtype=np.uint32)
+        check(lib().mcmc_chains_set_glibc_windows(self._h, u32ptr(w)))
+        st = (MCMCRunStats * self.chains)()
+        check(lib().mcmc_chains_run(self._h, max_sweeps, st))
+        check(lib().mcmc_chains_get_glibc_windows(self._h, u32ptr(w)))
+        self.glibc = [GlibcRand.__new__(GlibcRand) for _ in range(self.chains)]
+        for g, row in zip(self.glibc, w):
+            g.window = row.copy()
+        self._stats = list(st)
+        return self._stats
+
+    def stats(self) -> list[MCMCRunStats]:
+        return self._stats
+
+    def colorings(self) -> np.ndarray:
+        out = np.zeros((self.chains, self.graph.nNodes), dtype=np.uint32)
+        for r in range(self.chains):
+            check(lib().mcmc_chains_get_coloring(self._h, r, u32ptr(out[r])))
+        return out
+
+    def trajectories(self) -> list[np.ndarray]:
+        res = []
+        for r in range(self.chains):
+            n = ctypes.c_uint64()
+            check(lib().mcmc_chains_get_trajectory(self._h, r, None, 0, ctypes.byref(n)))
+            out = np.zeros(n.value, dtype=np.uint64)
+            if n.value:
+                check(lib().mcmc_chains_get_trajectory(self._h, r, u64ptr(out), n.value, ctypes.byref(n)))
+            res.append(out)
+        return res
+
+    def close(self) -> None:
+        if self._h:
+            lib().mcmc_chains_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CurandStates:
     """GPURand's per-vertex curandState array (GPURandomizer.cu:85-101: curand_init(seed, v, 0) for
     every vertex v) for the reference-GPU-semantics mode: cuRAND XORWOW states on the device, shared

@@ -1,0 +1,579 @@
+// mcmc_colorer_amd/csrc/chains.hip -- batched independent MCMC chains: one wave lane per chain.
+//
+// R chains of one graph run as one batch (mcmc_chains_*, include/mcmc_hip.h). Chain r is, bit for
+// bit, ColoringMCMC_CPU(g, params, seed + r).run() (graph_coloring/coloringMCMC_CPU.cpp:115-270) with
+// its OWN glibc rand() stream for the CDF-overflow fallback (:518) -- unlike --repet, whose
+// repetition i + 1 continues the process stream where repetition i stopped.
+//
+// Layout: colours are bytes, chain-minor in groups of 64 chains, C[buffer][group][v][64], double
+// buffered (C_t in buffer t & 1). One neighbour's colours of a whole group are 64 contiguous bytes,
+// and lane l of a wave is chain 64 group + l.
+//
+// Sweep (chains_sweep_kernel): a wave owns `vb` consecutive vertices of one group (blockIdx.y).
+//   drain   The row's neighbour ids are wave-uniform: 64 of them per coalesced load, the next 64
+//           prefetched meanwhile. A step loads four neighbours with one instruction: lane l the
+//           dword of chains 4 (l & 15) .. +3 of neighbour l >> 4 (256 B per wave-load; the id comes
+//           from the id register by ds_bpermute), eight steps in flight before the first use. Every
+//           lane ORs the bytes into four partial 64-bit occupancy masks. After 64 neighbours the
+//           masks are OR-reduced across the four 16-lane quarters (ds_bpermute xor 16 / 32, no LDS
+//           memory); when every live chain's mask holds all nCol colours the row's scan stops
+//           (count_free_colors, :361-383, cannot change any more: the result is the same). Slots past
+//           the row's end re-read the chunk's first neighbour (OR is idempotent): no predication.
+//   update  Lane l then takes chain l's mask (from lane l >> 2, word l & 3) and runs fill_p
+//           ("Baseline", :392-481) + extract_new_color (:492-528) for its chain: own colour,
+//           violation bit, Zv = popcount, the sequential fp32 CDF walk with strict `cdf > u`, the
+//           taboo counter. u is generate_canonical of engine draw initDraws_r + t n + v + 1: the
+//           state is x_r 16807^(t n + v0 + 1) at the block's first vertex (one table powmod, four
+//           mulmods) and one mulmod per vertex after it.
+//   out     C* bytes; the chain's violator count of C_t (per-lane sum over the block, LDS sum over
+//           the workgroup's waves, one atomic per workgroup and chain); one record {v, lane mask}
+//           per (group, vertex) with a CDF overflow in the group's append-only list -- at most n
+//           records per group, so the list cannot overflow.
+// Commit (chains_commit_kernel): one wave per chain. Appends the count to the chain's trajectory,
+//   applies `iter > maxRip` and `Cviol <= z` (a chain that stops keeps C_t: the sweep's output for
+//   it is discarded, no glibc draw is taken, and its lanes never write a buffer again), else serves
+//   the chain's overflow records in ascending vertex order (wave min-scan of the group's list per
+//   event -- events are ~1e-7 per draw) from the chain's glibc window: colour rand() % (nCol - 1)
+//   and the taboo value (:518-526). The last chain to stop makes later launches return at once.
+// Init (chains_init_kernel): one lane per chain walks default_random_engine(seed + r) through
+//   uniform_int_distribution(0, nCol - 1) in vertex order, rejections included (:53-61), so
+//   initDraws differs per chain and is exact without a host replay.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "mcmc_common.h"
+#include "rng.h"
+
+namespace mcmc {
+namespace {
+
+constexpr uint32_t kLanes = 64;              // chains per group = lanes per wave
+constexpr uint32_t kMaxChains = 1024;
+constexpr uint32_t kSweepWaves = 4;          // waves per sweep workgroup
+constexpr uint32_t kTrajCapMax = 1u << 20;   // trajectory entries kept per chain, as mcmc_run
+constexpr uint32_t kPollSweeps = 8;          // sweeps between two reads of the all-done counter
+
+struct ChainState {      // per chain, device
+    uint32_t done, iter, maxIter, buf;
+    uint32_t finalViol, head, draws_lo, draws_hi;   // head: the glibc ring's oldest word
+};
+
+struct ChainArgs {
+    const uint64_t* row_off;
+    const uint32_t* col_idx;
+    uint64_t m;
+    uint32_t n, R, G, nCol, vb;
+    uint32_t taboo_it, z, maxRip, traj_cap;
+    float eps;
+    uint8_t* C[2];          // [G][n][64]
+    uint32_t* taboo;        // [G][n][64], nullptr when tabooIteration == 0
+    uint32_t* xinit;        // [G * 64] engine state after the initial colouring
+    uint64_t* init_draws;   // [G * 64]
+    const uint32_t* powtab; // [4][256]: 16807^(b 256^k)
+    uint32_t* viol;         // [G * 64] violators of C_t, zeroed by the commit
+    uint32_t* evcnt;        // [2][G] overflow records of sweep t in evcnt[t & 1]
+    uint4* evlist;          // [G][n] {v, lanes 0..31, lanes 32..63, 0}
+    ChainState* st;         // [G * 64]
+    uint32_t* ring;         // [G * 64][31] glibc windows as rings
+    uint32_t* traj;         // [R][traj_cap]
+    uint32_t* ndone;        // chains that stopped
+};
+
+__device__ __forceinline__ uint64_t shfl64(uint64_t x, int src) {
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)x, src, 64);
+    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(x >> 32), src, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t or_xor64(uint64_t x, int lane_mask) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)x, lane_mask, 64);
+    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), lane_mask, 64);
+    return x | (((uint64_t)hi << 32) | lo);
+}
+
+// K steps of the drain from step s0 of the chunk whose ids `cur` holds (lane j: neighbour j of the
+// chunk, `rem` of them valid): K loads issued, then K x 4 bytes ORed into the partial masks.
+template <int K>
+__device__ __forceinline__ void drain_steps(const uint32_t* __restrict__ Cw, uint32_t cur, uint32_t s0, uint32_t rem,
+                                            uint32_t q, uint32_t i, uint32_t nmax, uint64_t (&m)[4]) {
+    uint32_t w[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const uint32_t e = (s0 + (uint32_t)k) * 4u + q;
+        const uint32_t id = min((uint32_t)__shfl((int)cur, (int)(e < rem ? e : 0u), 64), nmax);
+        w[k] = Cw[(size_t)id * 16u + i];
+    }
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) m[j] |= 1ull << ((w[k] >> (8 * j)) & 63u);
+    }
+}
+
+__global__ __launch_bounds__(64 * kSweepWaves) void chains_sweep_kernel(ChainArgs a, uint32_t t, uint32_t tn) {
+    if (*a.ndone >= a.R) return;   // every chain stopped (workgroup-uniform)
+    __shared__ uint32_t s_viol[kLanes];
+    const uint32_t lane = threadIdx.x & 63u, q = lane >> 4, i = lane & 15u;
+    const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t g = blockIdx.y, r = g * kLanes + lane;
+    if (threadIdx.x < kLanes) s_viol[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint64_t v0l = ((uint64_t)blockIdx.x * kSweepWaves + wid) * a.vb;
+    const bool live = r < a.R && a.st[r].done == 0u;
+    const uint64_t livemask = __ballot(live);
+    uint32_t nviol = 0u;
+    if (v0l < a.n && livemask != 0ull) {
+        const uint32_t v0 = (uint32_t)v0l, v1 = (uint32_t)min((uint64_t)a.n, v0l + a.vb);
+        const uint32_t n = a.n, nCol = a.nCol;
+        const size_t gofs = (size_t)g * n * kLanes;
+        const uint8_t* __restrict__ Cb = a.C[t & 1u] + gofs;
+        const uint32_t* __restrict__ Cw = reinterpret_cast<const uint32_t*>(Cb);
+        uint8_t* __restrict__ Cn = a.C[(t + 1u) & 1u] + gofs;
+        uint32_t* __restrict__ tab = a.taboo ? a.taboo + gofs : nullptr;
+        const uint64_t full = nCol == 64u ? ~0ull : (1ull << nCol) - 1ull;
+        // the four chains this lane's partial masks belong to that are not live count as full
+        const uint32_t dead4 = ~(uint32_t)(livemask >> (4u * i)) & 15u;
+        const float eps = a.eps, hi = 1.0f - (float)(nCol - 1u) * eps;   // :402-412, :471-479
+        // engine state of the block's first vertex: x_r 16807^(t n + v0 + 1)
+        uint64_t e = (uint64_t)tn + v0 + 1ull;
+        while (e >= kMinstdN) e -= kMinstdN;
+        uint32_t pw = 1u;
+        for (int k = 0; k < 4; k++) pw = minstd_mulmod(pw, a.powtab[k * 256 + (int)((e >> (8 * k)) & 255u)]);
+        uint32_t x = live ? minstd_mulmod(a.xinit[r], pw) : 1u;
+        for (uint32_t v = v0; v < v1; v++) {
+            const uint64_t end = min(a.row_off[v + 1], a.m), base = min(a.row_off[v], end);
+            const uint64_t deg = end - base;
+            uint64_t m[4] = {0ull, 0ull, 0ull, 0ull};
+            uint32_t ids = lane < deg ? a.col_idx[base + lane] : 0u;
+            for (uint64_t c0 = 0; c0 < deg; c0 += 64u) {
+                const uint32_t cur = ids;
+                const uint64_t nx = c0 + 64u + lane;
+                ids = nx < deg ? a.col_idx[base + nx] : 0u;   // the next chunk's ids, in flight during this one
+                const uint32_t rem = (uint32_t)min((uint64_t)64u, deg - c0);
+                for (uint32_t s = 0; 4u * s < rem;) {
+                    if (rem - 4u * s > 16u) {
+                        drain_steps<8>(Cw, cur, s, rem, q, i, n - 1u, m);
+                        s += 8u;
+                    } else {
+                        drain_steps<4>(Cw, cur, s, rem, q, i, n - 1u, m);
+                        s += 4u;
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < 4; j++) m[j] = or_xor64(or_xor64(m[j], 16), 32);
+                bool mine = true;
+#pragma unroll
+                for (int j = 0; j < 4; j++) mine = mine && (m[j] == full || ((dead4 >> j) & 1u));
+                if (__all(mine)) break;
+            }
+            // chain `lane`: word lane & 3 of lane lane >> 2
+            const int src = (int)(lane >> 2);
+            const uint64_t t0 = shfl64(m[0], src), t1 = shfl64(m[1], src), t2 = shfl64(m[2], src), t3 = shfl64(m[3], src);
+            const uint32_t jj = lane & 3u;
+            const uint64_t mask = (jj == 0u ? t0 : jj == 1u ? t1 : jj == 2u ? t2 : t3) & full;
+            const uint32_t c = Cb[(size_t)v * kLanes + lane];
+            const bool viol = (mask >> c) & 1ull;
+            nviol += (live && viol) ? 1u : 0u;
+            const uint32_t Zv = (uint32_t)__popcll(mask), fr = nCol - Zv;
+            uint32_t tb = tab ? tab[(size_t)v * kLanes + lane] : 0u;
+            uint32_t newc = c;
+            bool ovf = false;
+            const bool walk = live && tb == 0u;
+            if (__any(walk)) {
+                const float u = minstd_canonical(x);
+                const bool own = !viol || fr == 0u;
+                const uint64_t S = own ? (1ull << c) : ~mask;   // colours whose p is ps; eps elsewhere
+                const float ps = own ? hi : (1.0f - eps * (float)Zv) / (float)fr;
+                float cdf = 0.0f;
+                uint32_t idx = nCol;
+                for (uint32_t k0 = 0; k0 < nCol; k0 += 8u) {
+                    const uint32_t k1 = min(k0 + 8u, nCol);
+                    for (uint32_t k = k0; k < k1; k++) {
+                        cdf += ((S >> k) & 1ull) ? ps : eps;
+                        if (idx == nCol && cdf > u) idx = k;   // strict >, the first colour only (:510-514)
+                    }
+                    if (__all(!walk || idx != nCol)) break;
+                }
+                if (walk) {
+                    ovf = idx == nCol;
+                    newc = ovf ? c : idx;
+                    tb = (newc == c) ? a.taboo_it : 0u;   // :526 (an overflow's is written by the commit)
+                }
+            }
+            if (live && !walk) tb--;   // :496-501
+            if (live) {
+                Cn[(size_t)v * kLanes + lane] = (uint8_t)newc;
+                if (tab) tab[(size_t)v * kLanes + lane] = tb;
+            }
+            const uint64_t ob = __ballot(ovf);
+            if (ob != 0ull && lane == 0u) {
+                const uint32_t slot = atomicAdd(&a.evcnt[(t & 1u) * a.G + g], 1u);
+                if (slot < n) a.evlist[(size_t)g * n + slot] = make_uint4(v, (uint32_t)ob, (uint32_t)(ob >> 32), 0u);
+            }
+            x = minstd_mulmod(x, kMinstdA);
+        }
+        if (nviol) atomicAdd(&s_viol[lane], nviol);
+    }
+    __syncthreads();
+    if (threadIdx.x < kLanes && s_viol[threadIdx.x]) atomicAdd(&a.viol[g * kLanes + threadIdx.x], s_viol[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(64) void chains_commit_kernel(ChainArgs a, uint32_t t) {
+    const uint32_t r = blockIdx.x, lane = threadIdx.x, g = r >> 6, bit = r & 63u;
+    ChainState* s = a.st + r;
+    if (lane == 0u && bit == 0u) a.evcnt[((t + 1u) & 1u) * a.G + g] = 0u;   // the next sweep's counter
+    if (s->done) return;
+    uint32_t count = 0u;
+    if (lane == 0u) {
+        count = a.viol[r];
+        a.viol[r] = 0u;
+        if (t < a.traj_cap) a.traj[(size_t)r * a.traj_cap + t] = count;
+    }
+    count = (uint32_t)__shfl((int)count, 0, 64);
+    if (t > a.maxRip || count <= a.z) {   // :264-269 after maxRip + 1 sweeps, :136
+        if (lane == 0u) {
+            s->iter = t;
+            s->maxIter = t > a.maxRip ? 1u : 0u;
+            s->buf = t & 1u;
+            s->finalViol = count;
+            s->done = 1u;
+            atomicAdd(a.ndone, 1u);
+        }
+        return;
+    }
+    const uint32_t evc = min(a.evcnt[(t & 1u) * a.G + g], a.n);
+    if (evc == 0u) return;
+    const size_t gofs = (size_t)g * a.n * kLanes;
+    const uint8_t* Cc = a.C[t & 1u] + gofs;
+    uint8_t* Cn = a.C[(t + 1u) & 1u] + gofs;
+    const uint4* ev = a.evlist + (size_t)g * a.n;
+    uint32_t* ring = a.ring + (size_t)r * 31u;
+    uint32_t head = s->head, served = 0u;
+    int64_t last = -1;
+    for (;;) {   // the chain's events in ascending vertex order (:183-204 draws them in that order)
+        uint32_t best = 0xFFFFFFFFu;
+        for (uint32_t k = lane; k < evc; k += 64u) {
+            const uint4 e = ev[k];
+            const uint32_t lanes = bit < 32u ? e.y >> bit : e.z >> (bit - 32u);
+            if ((lanes & 1u) && (int64_t)e.x > last) best = min(best, e.x);
+        }
+        for (int o = 32; o > 0; o >>= 1) best = min(best, (uint32_t)__shfl_xor((int)best, o, 64));
+        if (best == 0xFFFFFFFFu) break;
+        if (lane == 0u) {
+            const uint32_t nc = glibc_next(ring, head) % (a.nCol - 1u);   // :518
+            const size_t at = (size_t)best * kLanes + bit;
+            Cn[at] = (uint8_t)nc;
+            if (a.taboo) a.taboo[gofs + at] = (nc == Cc[at]) ? a.taboo_it : 0u;   // :526
+        }
+        served++;
+        last = (int64_t)best;
+    }
+    if (lane == 0u && served) {
+        const uint64_t d = (((uint64_t)s->draws_hi << 32) | s->draws_lo) + served;
+        s->draws_lo = (uint32_t)d;
+        s->draws_hi = (uint32_t)(d >> 32);
+        s->head = head;
+    }
+}
+
+__global__ __launch_bounds__(64) void chains_init_kernel(ChainArgs a, uint32_t seed0, UniformIntConst k) {
+    const uint32_t lane = threadIdx.x, g = blockIdx.x, r = g * kLanes + lane;
+    const bool live = r < a.R;
+    uint8_t* C0 = a.C[0] + (size_t)g * a.n * kLanes;
+    uint32_t x = minstd_seed_state(seed0 + r);
+    uint64_t draws = 0;
+    for (uint32_t v = 0; v < a.n; v++) {
+        uint32_t col = 0u;
+        if (live) {
+            uint32_t rr;
+            do {   // uniform_int_distribution's rejection loop (libstdc++ uniform_int_dist.h)
+                x = minstd_mulmod(x, kMinstdA);
+                rr = x - 1u;
+                draws++;
+            } while (rr >= k.past);
+            col = rr / k.scaling;
+        }
+        C0[(size_t)v * kLanes + lane] = (uint8_t)col;
+    }
+    a.xinit[r] = x;
+    a.init_draws[r] = draws;
+}
+
+}  // namespace
+}  // namespace mcmc
+
+using namespace mcmc;
+
+struct mcmc_chains {
+    const mcmc_graph* g = nullptr;
+    mcmc_params p{};
+    ChainArgs a{};
+    void* mem = nullptr;          // one device allocation behind every pointer of `a`
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    uint32_t* pinned = nullptr;   // the all-done counter's host copy
+    uint32_t t = 0;               // sweeps launched so far
+    std::vector<uint64_t> init_draws;
+    std::vector<ChainState> st;   // as of the last run
+    std::vector<uint8_t> cache;   // get_coloring: one group's buffer
+    int cache_g = -1, cache_buf = -1;
+};
+
+namespace {
+
+int chains_sync_state(mcmc_chains* c) {
+    c->st.resize(c->a.R);
+    MCMC_HIP_TRY(hipMemcpyAsync(c->st.data(), c->a.st, sizeof(ChainState) * c->a.R, hipMemcpyDeviceToHost, c->stream));
+    MCMC_HIP_TRY(hipStreamSynchronize(c->stream));
+    for (auto& h : c->st)
+        if (!h.done) {   // still running (max_sweeps): t sweeps accepted, no final count (as mcmc_run)
+            h.iter = c->t;
+            h.buf = c->t & 1u;
+        }
+    return MCMC_OK;
+}
+
+int chains_upload_windows(mcmc_chains* c, const uint32_t* w /* [R][31], nullptr: srand(1) */) {
+    const uint32_t R = c->a.R;
+    std::vector<uint32_t> ring((size_t)R * 31u);
+    const GlibcWindow def = glibc_srand(1);
+    for (uint32_t r = 0; r < R; r++) std::memcpy(&ring[(size_t)r * 31u], w ? w + (size_t)r * 31u : def.r, 31u * sizeof(uint32_t));
+    int rc = chains_sync_state(c);
+    if (rc) return rc;
+    for (auto& s : c->st) s.head = 0u;
+    MCMC_HIP_TRY(hipMemcpy(c->a.ring, ring.data(), ring.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    MCMC_HIP_TRY(hipMemcpy(c->a.st, c->st.data(), sizeof(ChainState) * R, hipMemcpyHostToDevice));
+    return MCMC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mcmc_chains** out) {
+    if (!g || !p || !out) return fail(MCMC_E_ARG, "NULL argument");
+    *out = nullptr;
+    const GraphDev& gd = g->g;
+    if (p->nCol < 2 || p->nCol > 64)
+        return fail(MCMC_E_ARG, "chains: 2 <= nCol <= 64 (one 64-bit occupancy mask per lane), got " + std::to_string(p->nCol));
+    if (R < 1 || R > kMaxChains) return fail(MCMC_E_ARG, "chains: 1 <= R <= 1024, got " + std::to_string(R));
+    if (gd.n == 0) return fail(MCMC_E_ARG, "chains: empty graph");
+    if (!gd.row_off || gd.partial_rows)
+        return fail(MCMC_E_ARG, "chains: the graph needs a whole device CSR (mcmc_graph_upload / _simulate / _rmat, or "
+                                "mcmc_graph_materialize_csr after mcmc_graph_er_fast)");
+    MCMC_HIP_TRY(hipSetDevice(gd.device));
+    const uint32_t n = gd.n, G = (R + kLanes - 1) / kLanes, RP = G * kLanes;
+    const uint32_t traj_cap = (uint32_t)std::min<uint64_t>((uint64_t)p->maxRip + 2u, kTrajCapMax);
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_col = up((size_t)n * kLanes * G), b_tab = p->tabooIteration ? up(4 * (size_t)n * kLanes * G) : 0;
+    const size_t b_ev = up(sizeof(uint4) * (size_t)n * G), b_traj = up(4 * (size_t)R * traj_cap);
+    const size_t b_small = up(4 * RP) * 2 + up(8 * RP) + up(4 * 1024) + up(8 * G) + up(sizeof(ChainState) * RP) +
+                           up(4 * 31 * (size_t)RP) + 256;
+    const size_t need = 2 * b_col + b_tab + b_ev + b_traj + b_small;
+    size_t fr = 0, tot = 0;
+    MCMC_HIP_TRY(hipMemGetInfo(&fr, &tot));
+    if (need > fr)
+        return fail(MCMC_E_NOMEM, "chains: " + std::to_string(need) + " bytes needed (colours 2 x " + std::to_string(b_col) +
+                                      ", taboo " + std::to_string(b_tab) + ", overflow records " + std::to_string(b_ev) +
+                                      ", trajectories " + std::to_string(b_traj) + "), " + std::to_string(fr) + " free");
+    mcmc_chains* c = new mcmc_chains();
+    c->g = g;
+    c->p = *p;
+    hipError_t e = hipMalloc(&c->mem, need);
+    if (e == hipSuccess) e = hipMemset(c->mem, 0, need);
+    if (e == hipSuccess) e = hipStreamCreate(&c->stream);
+    if (e == hipSuccess) e = hipEventCreate(&c->ev0);
+    if (e == hipSuccess) e = hipEventCreate(&c->ev1);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&c->pinned), 64);
+    if (e != hipSuccess) {
+        mcmc_chains_destroy(c);
+        return fail(e == hipErrorOutOfMemory ? MCMC_E_NOMEM : MCMC_E_HIP,
+                    std::string("chains: allocation of ") + std::to_string(need) + " bytes: " + hipGetErrorString(e));
+    }
+    ChainArgs& a = c->a;
+    uint8_t* at = static_cast<uint8_t*>(c->mem);
+    auto take = [&](size_t b) { uint8_t* q = at; at += up(b); return q; };
+    a.C[0] = take(b_col);
+    a.C[1] = take(b_col);
+    a.taboo = b_tab ? reinterpret_cast<uint32_t*>(take(b_tab)) : nullptr;
+    a.evlist = reinterpret_cast<uint4*>(take(b_ev));
+    a.traj = reinterpret_cast<uint32_t*>(take(b_traj));
+    a.xinit = reinterpret_cast<uint32_t*>(take(4 * RP));
+    a.viol = reinterpret_cast<uint32_t*>(take(4 * RP));
+    a.init_draws = reinterpret_cast<uint64_t*>(take(8 * RP));
+    uint32_t* powtab = reinterpret_cast<uint32_t*>(take(4 * 1024));
+    a.powtab = powtab;
+    a.evcnt = reinterpret_cast<uint32_t*>(take(8 * G));
+    a.st = reinterpret_cast<ChainState*>(take(sizeof(ChainState) * RP));
+    a.ring = reinterpret_cast<uint32_t*>(take(4 * 31 * (size_t)RP));
+    a.ndone = reinterpret_cast<uint32_t*>(take(4));
+    a.row_off = gd.row_off;
+    a.col_idx = gd.col_idx;
+    a.m = gd.m;
+    a.n = n;
+    a.R = R;
+    a.G = G;
+    a.nCol = p->nCol;
+    a.eps = p->epsilon;
+    a.taboo_it = p->tabooIteration;
+    a.z = p->tailcut ? std::max<uint32_t>(50u, n / 2000u) : 0u;   // :89-97
+    a.maxRip = p->maxRip;
+    a.traj_cap = traj_cap;
+    // vertices per wave: 16, more once the grid has ~8 waves per SIMD of a 256-CU device anyway
+    a.vb = (uint32_t)std::min<uint64_t>(64u, std::max<uint64_t>(16u, ((uint64_t)n * G + 8191u) / 8192u));
+    if (const char* s = getenv("MCMC_CHAINS_VB")) a.vb = std::min(1024u, std::max(1u, (uint32_t)atoi(s)));
+    std::vector<uint32_t> tab(1024);
+    for (uint32_t k = 0; k < 4; k++) {
+        const uint32_t b = minstd_pow(kMinstdA, 1ull << (8 * k));
+        tab[k * 256] = 1u;
+        for (uint32_t j = 1; j < 256; j++) tab[k * 256 + j] = minstd_mulmod(tab[k * 256 + j - 1], b);
+    }
+    e = hipMemcpy(powtab, tab.data(), 4096, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        chains_init_kernel<<<G, 64, 0, c->stream>>>(a, p->seed, uniform_int_const(p->nCol));
+        e = hipGetLastError();
+    }
+    c->init_draws.resize(RP);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(c->init_draws.data(), a.init_draws, 8 * (size_t)RP, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    int rc = e == hipSuccess ? chains_upload_windows(c, nullptr) : fail(MCMC_E_HIP, std::string("chains init: ") + hipGetErrorString(e));
+    if (rc) {
+        mcmc_chains_destroy(c);
+        return rc;
+    }
+    *out = c;
+    return MCMC_OK;
+}
+
+int mcmc_chains_set_glibc_windows(mcmc_chains* c, const uint32_t* windows) {
+    if (!c || !windows) return fail(MCMC_E_ARG, "NULL argument");
+    MCMC_HIP_TRY(hipSetDevice(c->g->g.device));
+    return chains_upload_windows(c, windows);
+}
+
+int mcmc_chains_set_tailcut_repair(mcmc_chains* c, uint32_t max_passes) {
+    if (!c) return fail(MCMC_E_ARG, "NULL context");
+    if (max_passes) return fail(MCMC_E_ARG, "chains: tail-cut repair is not supported (run the chain with mcmc_run)");
+    return MCMC_OK;
+}
+
+int mcmc_chains_get_glibc_windows(mcmc_chains* c, uint32_t* windows) {
+    if (!c || !windows) return fail(MCMC_E_ARG, "NULL argument");
+    MCMC_HIP_TRY(hipSetDevice(c->g->g.device));
+    int rc = chains_sync_state(c);
+    if (rc) return rc;
+    std::vector<uint32_t> ring((size_t)c->a.R * 31u);
+    MCMC_HIP_TRY(hipMemcpy(ring.data(), c->a.ring, ring.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < c->a.R; r++)
+        for (uint32_t i = 0; i < 31; i++) windows[(size_t)r * 31u + i] = ring[(size_t)r * 31u + (c->st[r].head + i) % 31u];
+    return MCMC_OK;
+}
+
+int mcmc_chains_run(mcmc_chains* c, uint32_t max_sweeps, mcmc_run_stats* stats) {
+    if (!c) return fail(MCMC_E_ARG, "NULL context");
+    MCMC_HIP_TRY(hipSetDevice(c->g->g.device));
+    const ChainArgs& a = c->a;
+    // at most maxRip + 2 sweeps in all: the last one only counts (:264-269)
+    const uint64_t cap = (uint64_t)a.maxRip + 2u;
+    const uint64_t left = cap > c->t ? cap - c->t : 0u;
+    const uint32_t total = (uint32_t)(max_sweeps ? std::min<uint64_t>(max_sweeps, left) : left);
+    const dim3 grid((uint32_t)(((uint64_t)a.n + (uint64_t)a.vb * kSweepWaves - 1) / ((uint64_t)a.vb * kSweepWaves)), a.G);
+    c->cache_g = -1;
+    MCMC_HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    // The all-done counter is read every kPollSweeps sweeps: a read drains the stream (~20 us), a
+    // sweep + commit pair of a small graph is ~10 us, and the at most kPollSweeps - 1 pairs launched
+    // past the last stop return at their first instruction.
+    for (uint32_t k = 0; k < total;) {
+        const uint32_t b = std::min(kPollSweeps, total - k);
+        for (uint32_t j = 0; j < b; j++, c->t++) {
+            const uint32_t tn = (uint32_t)(((uint64_t)c->t * a.n) % kMinstdN);
+            chains_sweep_kernel<<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+            chains_commit_kernel<<<a.R, 64, 0, c->stream>>>(a, c->t);
+        }
+        MCMC_HIP_TRY(hipGetLastError());
+        k += b;
+        MCMC_HIP_TRY(hipMemcpyAsync(c->pinned, a.ndone, 4, hipMemcpyDeviceToHost, c->stream));
+        MCMC_HIP_TRY(hipStreamSynchronize(c->stream));
+        if (*c->pinned >= a.R) break;
+    }
+    MCMC_HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    MCMC_HIP_TRY(hipEventSynchronize(c->ev1));
+    float ms = 0;
+    MCMC_HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    int rc = chains_sync_state(c);
+    if (rc) return rc;
+    for (uint32_t r = 0; r < a.R; r++) {
+        const ChainState& h = c->st[r];
+        if (!stats) break;
+        mcmc_run_stats s{};
+        s.iter = h.iter;
+        s.maxIterReached = h.done ? (int32_t)h.maxIter : 0;
+        s.finalViol = h.done ? h.finalViol : ~0ull;
+        s.trajLen = std::min<uint64_t>((uint64_t)h.iter + (h.done ? 1u : 0u), a.traj_cap);
+        s.glibcDraws = ((uint64_t)h.draws_hi << 32) | h.draws_lo;
+        s.initDraws = c->init_draws[r];
+        s.loopMs = ms;
+        s.sweepsRun = h.iter + (h.done ? 1u : 0u);
+        stats[r] = s;
+    }
+    return MCMC_OK;
+}
+
+int mcmc_chains_get_coloring(mcmc_chains* c, uint32_t r, uint32_t* out) {
+    if (!c || !out) return fail(MCMC_E_ARG, "NULL argument");
+    if (r >= c->a.R) return fail(MCMC_E_ARG, "chain index out of range");
+    MCMC_HIP_TRY(hipSetDevice(c->g->g.device));
+    const uint32_t n = c->a.n;
+    if (c->st.size() != c->a.R) {
+        int rc = chains_sync_state(c);
+        if (rc) return rc;
+    }
+    const int g = (int)(r / kLanes), buf = (int)c->st[r].buf;
+    if (g != c->cache_g || buf != c->cache_buf) {   // one download serves the group's chains
+        c->cache.resize((size_t)n * kLanes);
+        MCMC_HIP_TRY(hipMemcpy(c->cache.data(), c->a.C[buf] + (size_t)g * n * kLanes, c->cache.size(), hipMemcpyDeviceToHost));
+        c->cache_g = g;
+        c->cache_buf = buf;
+    }
+    for (uint32_t v = 0; v < n; v++) out[v] = c->cache[(size_t)v * kLanes + (r % kLanes)];
+    return MCMC_OK;
+}
+
+int mcmc_chains_get_trajectory(mcmc_chains* c, uint32_t r, uint64_t* out, uint64_t cap, uint64_t* len) {
+    if (!c || !len) return fail(MCMC_E_ARG, "NULL argument");
+    if (r >= c->a.R) return fail(MCMC_E_ARG, "chain index out of range");
+    MCMC_HIP_TRY(hipSetDevice(c->g->g.device));
+    if (c->st.size() != c->a.R) {
+        int rc = chains_sync_state(c);
+        if (rc) return rc;
+    }
+    const ChainState& h = c->st[r];
+    const uint64_t have = std::min<uint64_t>(h.done ? (uint64_t)h.iter + 1u : c->t, c->a.traj_cap);
+    *len = have;
+    const uint64_t k = out ? std::min(have, cap) : 0u;
+    if (k) {
+        std::vector<uint32_t> tmp(k);
+        MCMC_HIP_TRY(hipMemcpy(tmp.data(), c->a.traj + (size_t)r * c->a.traj_cap, 4 * k, hipMemcpyDeviceToHost));
+        for (uint64_t j = 0; j < k; j++) out[j] = tmp[j];
+    }
+    return MCMC_OK;
+}
+
+void mcmc_chains_destroy(mcmc_chains* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->g->g.device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->mem) (void)hipFree(c->mem);
+    if (c->pinned) (void)hipHostFree(c->pinned);
+    if (c->ev0) (void)hipEventDestroy(c->ev0);
+    if (c->ev1) (void)hipEventDestroy(c->ev1);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    delete c;
+}
+
+}  // extern "C"

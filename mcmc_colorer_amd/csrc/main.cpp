@@ -9,6 +9,8 @@
 //   same sweep; outputs <graph>-MCMC_GPU-<i>.log in coloringMCMC_prints.cu's layout
 //   --tailcutRepair: after the loop, run the reference's tail cut (coloringMCMC_CPU.cpp:272-311)
 //   with its inner loop fixed (k++; the reference's never returns), at most 1000 passes
+//   --chains R: with --mcmcgpu, seeds seed .. seed + R - 1 as one batch (csrc/chains.hip), each chain on
+//   its own copy of the glibc stream; writes the files --repet R names
 // Outputs <outDir>/<graphName>-MCMC_GPU-<i>.log and -colors.txt per repetition.
 // --mcmccpu: ColoringMCMC_CPU's surface (-MCMC_CPU-<i> files, seed + i), run by the same HIP sweep --
 // the CPU colorer's results, bit for bit (the oracle, oracle/build/mcmc_cpu_ref, is test infrastructure);
@@ -121,6 +123,8 @@ void help(const char* argv0) {
               << "  --tailcut            stop at Cviol <= max(50, n/2000)\n"
               << "  --tailcutRepair      then repair the remaining conflicts (corrected tail cut, <= 1000 passes)\n"
               << "  --repet N            repetitions, seeds seed+i (default 1)\n"
+              << "  --chains R           --mcmcgpu: seeds seed .. seed+R-1 as ONE batch, a wave lane per chain\n"
+              << "                       (nCol <= 64, R <= 1024; each chain its own glibc stream; not with --repet / --gpus)\n"
               << "  --seed N             seed (default: time, which also srand()s glibc)\n"
               << "  --outDir D           output directory\n"
               << "  --device D           HIP device (default 0)\n"
@@ -134,7 +138,8 @@ void help(const char* argv0) {
 int main(int argc, char** argv) {
     std::string graphFilename, outDir;
     double prob = 0.0, numColRatio = 0.0;
-    uint32_t n = 0, nCol = 0, seed = 0, repetitions = 1, tabooIteration = 0;
+    uint32_t n = 0, nCol = 0, seed = 0, repetitions = 1, tabooIteration = 0, chains = 0;
+    bool repetSet = false;
     bool simulate = false, mcmccpu = false, mcmcgpu = false, tailcut = false, fast = false,
          tailcutRepair = false, mcmcgpuref = false, greedyff = false, lubygpu = false, vffgpu = false;
     uint64_t erSeed = 1;
@@ -152,6 +157,7 @@ int main(int argc, char** argv) {
         {"device", required_argument, 0, 'D'},   {"simulate-fast", required_argument, 0, 'F'},
         {"er-seed", required_argument, 0, 'E'},  {"tailcutRepair", no_argument, 0, 'X'},
         {"mcmcgpu-ref", no_argument, 0, 'G'},    {"gpus", required_argument, 0, 'P'}, {"loopback", no_argument, 0, 'L'},
+        {"chains", required_argument, 0, 'C'},
         {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "g:o:s:n:12345k:r:t:lR:S:hD:", longopts, nullptr)) != -1) {
@@ -172,7 +178,8 @@ int main(int argc, char** argv) {
                 case 'r': numColRatio = std::stod(optarg); if (numColRatio < 1.0 || numColRatio > 16.0) throw 1; break;
                 case 't': if (std::stoi(optarg) < 1) throw 1; tabooIteration = std::stoi(optarg); break;
                 case 'l': tailcut = true; break;
-                case 'R': if (std::stoi(optarg) < 1) throw 1; repetitions = std::stoi(optarg); break;
+                case 'R': if (std::stoi(optarg) < 1) throw 1; repetitions = std::stoi(optarg); repetSet = true; break;
+                case 'C': if (std::stoi(optarg) < 1) throw 1; chains = std::stoi(optarg); break;
                 case 'S': seed = (uint32_t)std::stoi(optarg); break;
                 case 'D': device = std::stoi(optarg); break;
                 case 'F': simulate = fast = true; prob = std::stod(optarg);
@@ -202,6 +209,12 @@ int main(int argc, char** argv) {
     if (!mcmcgpu && !mcmcgpuref && !mcmccpu && !greedyff && !lubygpu && !vffgpu) {
         std::cout << "No coloring algorithm specified: enabling MCMC GPU (--mcmcgpu)" << std::endl;
         mcmcgpu = true;
+    }
+    if (chains && (repetSet || gpus > 1 || !mcmcgpu || mcmccpu || greedyff || lubygpu || vffgpu || tailcutRepair ||
+                   chains > 1024 || nCol > 64)) {
+        std::cout << "--chains R batches --mcmcgpu alone: 1 <= R <= 1024, --nCol <= 64, no --repet, --gpus > 1, "
+                     "--tailcutRepair or other colorer" << std::endl;
+        return 255;
     }
     if (simulate && n == 0) { std::cout << "Simualtion enabled: specify the number of nodes (-n)." << std::endl; return 255; }
     if (numColRatio == 0.0) numColRatio = 1.0;
@@ -276,6 +289,31 @@ int main(int argc, char** argv) {
 
     GPURand GPURandGen(g->getNNodes(), (long)seed);
     CurandStates* curand = (mcmcgpuref || lubygpu) ? new CurandStates(g->getNNodes(), (long)seed, device) : nullptr;   // main.cu:80
+    if (chains) {   // one batch instead of the repetition loop
+        ColoringMCMCParams params;                                   // main.cu:160-168
+        params.numColorRatio = numColorRatio;
+        params.nCol = (nCol != 0) ? nCol : (col_sz)(g->getMaxNodeDeg() * numColorRatio);
+        params.epsilon = 1e-8f;
+        params.lambda = 1.0f;
+        params.ratioFreezed = 1e-2f;
+        params.maxRip = 250;
+        params.tabooIteration = tabooIteration;
+        params.tailcut = tailcut;
+        if (params.nCol > 64) {
+            std::cout << "--chains needs nCol <= 64 (default nCol = " << params.nCol << ": give --nCol)" << std::endl;
+            return 255;
+        }
+        ColoringMCMCChains<float, float> batch(g, GPURandGen.randStates, params, chains);
+        batch.run();
+        uint64_t sweeps = 0;
+        for (uint32_t r = 0; r < chains; r++) {
+            batch.save(r, outDir + "/" + graphName + "-MCMC_GPU-" + std::to_string(r));
+            sweeps += batch.getStats(r).iter;
+        }
+        std::cout << "MCMC GPU chains elapsed time: " << batch.getStats(0).loopMs / 1000.0 << " (" << chains
+                  << " chains, " << sweeps << " chain-sweeps)" << std::endl;
+        repetitions = 0;
+    }
     for (uint32_t i = 0; i < repetitions; i++) {
         std::cout << "Repetition: " << i << std::endl;
         if (lubygpu) {   // main.cu:89-109 (first: it advances the shared states)
