@@ -378,11 +378,7 @@ public:
         p.tabooIteration = param.tabooIteration;
         p.tailcut = param.tailcut;
         p.seed = seed;
-        const uint64_t* ro = nullptr;
-        const uint32_t* ci = nullptr;
-        if (mcmc_graph_device_ptrs(graph->handle(), &ro, &ci) != MCMC_OK)   // a generated graph: the chains scan a CSR
-            MCMC_CHECK(mcmc_graph_materialize_csr(const_cast<mcmc_graph*>(graph->handle())));
-        MCMC_CHECK(mcmc_chains_create(graph->handle(), &p, R, &ctx));
+        MCMC_CHECK(mcmc_chains_create(graph->handle(), &p, R, &ctx));   // a generated graph: its tiled layout, no CSR
         MCMC_CHECK(mcmc_chains_set_tailcut_repair(ctx, param.tailcutRepair));
         std::vector<uint32_t> w((size_t)R * 31);
         for (uint32_t r = 0; r < R; r++) std::memcpy(&w[(size_t)r * 31], mcmc::glibc_global().w, 31 * sizeof(uint32_t));
@@ -394,6 +390,13 @@ public:
     }
 
     uint32_t chains() const { return R; }
+    // mcmc_chains_get_info: {adjacency source (0 CSR, 1 tiled layout), device bytes of the batch,
+    // vertices per wave, chain groups, sweep grid x, 0, 0, 0}; after run().
+    std::vector<uint64_t> info() const {
+        std::vector<uint64_t> w(8);
+        MCMC_CHECK(mcmc_chains_get_info(ctx, w.data()));
+        return w;
+    }
     const mcmc_run_stats& getStats(uint32_t r) const { return stats.at(r); }
     std::vector<uint32_t> getColoring(uint32_t r) const {
         std::vector<uint32_t> c(graph->getNNodes());

@@ -261,14 +261,19 @@ void mcmc_destroy(mcmc_ctx* c);
  * stopped: chain r equals repetition r only when both start at the same window (always, while no
  * overflow occurs -- ~1e-7 per draw at the default epsilon).
  * Supported: 2 <= nCol <= 64 (one 64-bit occupancy mask per lane), 1 <= R <= 1024, a graph with a
- * whole device CSR (mcmc_graph_upload, _simulate, _rmat, or mcmc_graph_materialize_csr after
- * mcmc_graph_er_fast); anything else is MCMC_E_ARG. Device memory: 2 n 64 ceil(R / 64) bytes of
+ * whole device CSR (mcmc_graph_upload, _simulate, _rmat) or, when it has none, the full-range tiled
+ * layout of mcmc_graph_er_fast, which the sweep reads as it is (block-local 16-bit ids; no CSR is
+ * built, so the batch also runs where a CSR would not fit). A row-range graph
+ * (mcmc_graph_er_fast_rows / _part) and anything else is MCMC_E_ARG. Device memory: 2 n 64 ceil(R / 64) bytes of
  * colours, 4 times half of that again for the taboo counters when tabooIteration > 0, 16 n
  * ceil(R / 64) bytes of overflow records, the trajectories; MCMC_E_NOMEM with the byte counts when
  * it does not fit. The context borrows `g`. */
 typedef struct mcmc_chains mcmc_chains;
 /* params.seed is chain 0's seed. Draws every chain's initial colouring (mcmc_init_coloring's). */
 int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mcmc_chains** out);
+/* out[0] adjacency source of the sweep (0 CSR, 1 tiled layout), [1] device bytes of the batch's own
+ * allocation, [2] vertices per wave, [3] chain groups, [4] sweep grid x, [5..7] 0. */
+int mcmc_chains_get_info(mcmc_chains* c, uint64_t out[8]);
 /* windows[R][31]; default: every chain at srand(1) with no draws (mcmc_set_glibc_window's default).
  * mcmc_chains_get_glibc_windows returns them advanced by each chain's glibcDraws. */
 int mcmc_chains_set_glibc_windows(mcmc_chains* c, const uint32_t* windows /* [R][31] */);

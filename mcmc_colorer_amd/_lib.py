@@ -65,6 +65,7 @@ SIGNATURES: dict[str, tuple] = {
     "mcmc_refstruct_bench": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, POINTER(c_double), _u64p]),
     "mcmc_destroy": (None, [c_void_p]),
     "mcmc_chains_create": (c_int, [c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
+    "mcmc_chains_get_info": (c_int, [c_void_p, _u64p]),
     "mcmc_chains_set_glibc_windows": (c_int, [c_void_p, _u32p]),
     "mcmc_chains_get_glibc_windows": (c_int, [c_void_p, _u32p]),
     "mcmc_chains_set_tailcut_repair": (c_int, [c_void_p, c_uint32]),

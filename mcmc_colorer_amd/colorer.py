@@ -362,15 +362,14 @@ class ColoringMCMCChains:
     every chain draws its CDF-overflow colours from its own glibc window (``glibc``: one GlibcRand
     whose position every chain starts at, or a list of ``chains`` of them; advanced in place by
     ``run()``), where ``ColoringMCMC.run(i + 1)`` continues the stream ``run(i)`` left. 2 <= nCol <= 64,
-    1 <= chains <= 1024, a graph with a device CSR; no tail-cut repair."""
+    1 <= chains <= 1024, a graph with a device CSR or a whole ``Graph.er_fast`` graph, whose tiled
+    16-bit layout the sweep reads as it is (no CSR is built); no tail-cut repair."""
 
     def __init__(self, graph: Graph, params: ColoringMCMCParams, seed: int, chains: int, glibc=None):
         if params.nCol == 0:
             params = ColoringMCMCParams(**{**params.__dict__, "nCol": default_ncol(graph, params)})
         self.graph, self.param, self.seed, self.chains = graph, params, seed, int(chains)
         self._h = ctypes.c_void_p()
-        if getattr(graph, "generated", False):
-            check(lib().mcmc_graph_materialize_csr(graph.handle))
         self._cparams = params.to_c(seed)
         check(lib().mcmc_chains_create(graph.handle, ctypes.byref(self._cparams), self.chains, ctypes.byref(self._h)))
         check(lib().mcmc_chains_set_tailcut_repair(self._h, int(params.tailcutRepair)))
@@ -393,6 +392,13 @@ class ColoringMCMCChains:
 
     def stats(self) -> list[MCMCRunStats]:
         return self._stats
+
+    def info(self) -> list[int]:
+        """mcmc_chains_get_info: [adjacency source (0 CSR, 1 tiled layout), device bytes of the batch,
+        vertices per wave, chain groups, sweep grid x, 0, 0, 0]."""
+        out = np.zeros(8, dtype=np.uint64)
+        check(lib().mcmc_chains_get_info(self._h, u64ptr(out)))
+        return [int(x) for x in out]
 
     def colorings(self) -> np.ndarray:
         out = np.zeros((self.chains, self.graph.nNodes), dtype=np.uint32)

@@ -10,8 +10,9 @@
 // and lane l of a wave is chain 64 group + l.
 //
 // Sweep (chains_sweep_kernel): a wave owns `vb` consecutive vertices of one group (blockIdx.y).
-//   drain   The row's neighbour ids are wave-uniform: 64 of them per coalesced load, the next 64
-//           prefetched meanwhile. A step loads four neighbours with one instruction: lane l the
+//   drain   The row's neighbour ids are wave-uniform: 64 of them per coalesced load (CSR) or per
+//           flattened chunk of the tiled 16-bit layout (below), the next 64 prefetched meanwhile. A
+//           step loads four neighbours with one instruction: lane l the
 //           dword of chains 4 (l & 15) .. +3 of neighbour l >> 4 (256 B per wave-load; the id comes
 //           from the id register by ds_bpermute), eight steps in flight before the first use. Every
 //           lane ORs the bytes into four partial 64-bit occupancy masks. After 64 neighbours the
@@ -19,6 +20,20 @@
 //           memory); when every live chain's mask holds all nCol colours the row's scan stops
 //           (count_free_colors, :361-383, cannot change any more: the result is the same). Slots past
 //           the row's end re-read the chunk's first neighbour (OR is idempotent): no predication.
+//   tiled   A generated graph (mcmc_graph_er_fast) has no CSR: its rows live in the tiled layout
+//           (TiledLayout, mcmc_common.h) as nblocks separate segments of block-local 16-bit ids,
+//           each padded to whole octets (8 ids) with copies of its first id. The second
+//           instantiation of the sweep flattens a row instead of walking segments (~6 ids each at
+//           n = 1e6, degree 100; many empty). Directory: per round of 64 blocks lane j reads the two
+//           table entries of block 64 round + j and keeps the segment's start and its count of
+//           real ids (padded length less the padding count in the entry's low 3 bits); a wave
+//           inclusive scan (__shfl_up) gives every segment its first and end slot in the round's
+//           stream of real ids. Chunk: lane j owns slot c0 + j; the owning segment is the number of
+//           segments that end at or before the slot (ends ascend, empty segments drop out), found
+//           by a binary search over the lanes' ends (six ds_bpermute); one more fetches the
+//           segment's start - first slot, the lane loads its 16-bit id and forms
+//           (block << block_log2) | id. From the id register on the drain is the CSR one, with the
+//           CSR's slot count; the exit test runs after every chunk, ahead of the next directory round.
 //   update  Lane l then takes chain l's mask (from lane l >> 2, word l & 3) and runs fill_p
 //           ("Baseline", :392-481) + extract_new_color (:492-528) for its chain: own colour,
 //           violation bit, Zv = popcount, the sequential fp32 CDF walk with strict `cdf > u`, the
@@ -67,6 +82,11 @@ struct ChainArgs {
     const uint64_t* row_off;
     const uint32_t* col_idx;
     uint64_t m;
+    // the full-range tiled layout of a generated graph (row_off == nullptr): chains_sweep_kernel<true>
+    const uint16_t* tcol;
+    const uint64_t* gbase;
+    const uint32_t* tseg;
+    uint32_t grp_rows, nblocks, block_log2;
     uint32_t n, R, G, nCol, vb;
     uint32_t taboo_it, z, maxRip, traj_cap;
     float eps;
@@ -114,6 +134,48 @@ __device__ __forceinline__ void drain_steps(const uint32_t* __restrict__ Cw, uin
     }
 }
 
+// One chunk of the drain, shared by the CSR and the tiled instantiation: the 4-neighbour steps over
+// the `rem` ids of `cur`, the OR-reduction of the partial masks over the four quarters, and the exit
+// test -- `all_full`: every live chain's mask is full. A macro, not a function: through a function
+// (forced inline) the CSR sweep compiled to 81 VGPRs instead of 63.
+#define MCMC_DRAIN_CHUNK(cur, rem, all_full)                                                        \
+    do {                                                                                            \
+        for (uint32_t s = 0; 4u * s < (rem);) {                                                     \
+            if ((rem) - 4u * s > 16u) {                                                             \
+                drain_steps<8>(Cw, (cur), s, (rem), q, i, n - 1u, m);                               \
+                s += 8u;                                                                            \
+            } else {                                                                                \
+                drain_steps<4>(Cw, (cur), s, (rem), q, i, n - 1u, m);                               \
+                s += 4u;                                                                            \
+            }                                                                                       \
+        }                                                                                           \
+        _Pragma("unroll") for (int j = 0; j < 4; j++) m[j] = or_xor64(or_xor64(m[j], 16), 32);      \
+        bool mine = true;                                                                           \
+        _Pragma("unroll") for (int j = 0; j < 4; j++)                                               \
+            mine = mine && (m[j] == full || ((dead4 >> j) & 1u));                                   \
+        all_full = __all(mine);                                                                     \
+    } while (0)
+
+// Tiled layout: the ids of slots c0 .. c0 + 63 of a directory round's flattened stream (lane j: slot
+// c0 + j). endo: the end slot of lane j's segment in the stream (ascending over the lanes); delta:
+// its start in the group's ids minus its first slot; b0: the round's first block. The owner of a
+// slot is the number of segments that end at or before it: a binary search over the lanes' endo, six
+// ds_bpermute. Slots past `total` read the group's first id (in bounds; the drain never uses them).
+__device__ __forceinline__ uint32_t tiled_chunk(const uint16_t* __restrict__ ids16, uint32_t delta, uint32_t endo,
+                                                uint32_t c0, uint32_t total, uint32_t b0, uint32_t block_log2,
+                                                uint32_t lane) {
+    const uint32_t p = c0 + lane;
+    uint32_t sg = 0u;
+#pragma unroll
+    for (uint32_t step = 32u; step > 0u; step >>= 1)
+        if ((uint32_t)__shfl((int)endo, (int)(sg + step - 1u), 64) <= p) sg += step;   // sg <= 63
+    const uint32_t d = (uint32_t)__shfl((int)delta, (int)sg, 64);
+    const bool in = p < total;
+    return (in ? (b0 + sg) << block_log2 : 0u) | ids16[in ? p + d : 0u];
+}
+
+// TILED = false: the rows come from the CSR; true: from the full-range tiled layout.
+template <bool TILED>
 __global__ __launch_bounds__(64 * kSweepWaves) void chains_sweep_kernel(ChainArgs a, uint32_t t, uint32_t tn) {
     if (*a.ndone >= a.R) return;   // every chain stopped (workgroup-uniform)
     __shared__ uint32_t s_viol[kLanes];
@@ -144,31 +206,65 @@ __global__ __launch_bounds__(64 * kSweepWaves) void chains_sweep_kernel(ChainArg
         uint32_t pw = 1u;
         for (int k = 0; k < 4; k++) pw = minstd_mulmod(pw, a.powtab[k * 256 + (int)((e >> (8 * k)) & 255u)]);
         uint32_t x = live ? minstd_mulmod(a.xinit[r], pw) : 1u;
+        // tiled: the layout group of v and v's row in it (a wave's rows may straddle two groups)
+        uint32_t grp = 0u, rg = 0u, tstride = 0u;
+        if constexpr (TILED) {
+            grp = v0 / a.grp_rows;
+            rg = v0 - grp * a.grp_rows;
+            tstride = tseg_stride(a.grp_rows);
+        }
         for (uint32_t v = v0; v < v1; v++) {
-            const uint64_t end = min(a.row_off[v + 1], a.m), base = min(a.row_off[v], end);
-            const uint64_t deg = end - base;
             uint64_t m[4] = {0ull, 0ull, 0ull, 0ull};
-            uint32_t ids = lane < deg ? a.col_idx[base + lane] : 0u;
-            for (uint64_t c0 = 0; c0 < deg; c0 += 64u) {
-                const uint32_t cur = ids;
-                const uint64_t nx = c0 + 64u + lane;
-                ids = nx < deg ? a.col_idx[base + nx] : 0u;   // the next chunk's ids, in flight during this one
-                const uint32_t rem = (uint32_t)min((uint64_t)64u, deg - c0);
-                for (uint32_t s = 0; 4u * s < rem;) {
-                    if (rem - 4u * s > 16u) {
-                        drain_steps<8>(Cw, cur, s, rem, q, i, n - 1u, m);
-                        s += 8u;
-                    } else {
-                        drain_steps<4>(Cw, cur, s, rem, q, i, n - 1u, m);
-                        s += 4u;
+            if constexpr (!TILED) {
+                const uint64_t end = min(a.row_off[v + 1], a.m), base = min(a.row_off[v], end);
+                const uint64_t deg = end - base;
+                uint32_t ids = lane < deg ? a.col_idx[base + lane] : 0u;
+                for (uint64_t c0 = 0; c0 < deg; c0 += 64u) {
+                    const uint32_t cur = ids;
+                    const uint64_t nx = c0 + 64u + lane;
+                    ids = nx < deg ? a.col_idx[base + nx] : 0u;   // the next chunk's ids, in flight during this one
+                    const uint32_t rem = (uint32_t)min((uint64_t)64u, deg - c0);
+                    bool all_full;
+                    MCMC_DRAIN_CHUNK(cur, rem, all_full);
+                    if (all_full) break;
+                }
+            } else {
+                const uint16_t* __restrict__ ids16 = a.tcol + a.gbase[grp];
+                const uint32_t* __restrict__ ts = a.tseg + (size_t)grp * a.nblocks * tstride + rg;
+                bool rowfull = false;
+                for (uint32_t b0 = 0; b0 < a.nblocks && !rowfull; b0 += 64u) {
+                    // directory of blocks b0 .. b0 + 63: lane j its segment's start and its real ids
+                    // (the padded length less the padding count in the entry's low 3 bits)
+                    uint32_t seg0 = 0u, len = 0u;
+                    if (b0 + lane < a.nblocks) {
+                        const uint32_t* ent = ts + (size_t)(b0 + lane) * tstride;
+                        const uint32_t e0 = ent[0];
+                        seg0 = e0 & kTsegPos;
+                        len = (ent[1] & kTsegPos) - seg0 - (e0 & 7u);
+                    }
+                    uint32_t endo = len;   // inclusive scan: the segment's end slot in the round's stream
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const uint32_t y = (uint32_t)__shfl_up((int)endo, o, 64);
+                        if (lane >= (uint32_t)o) endo += y;
+                    }
+                    const uint32_t delta = seg0 - (endo - len);
+                    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)endo, 63);
+                    if (total == 0u) continue;
+                    uint32_t ids = tiled_chunk(ids16, delta, endo, 0u, total, b0, a.block_log2, lane);
+                    for (uint32_t c0 = 0; c0 < total; c0 += 64u) {
+                        const uint32_t cur = ids;
+                        if (c0 + 64u < total)   // the next chunk's ids, in flight during this one
+                            ids = tiled_chunk(ids16, delta, endo, c0 + 64u, total, b0, a.block_log2, lane);
+                        const uint32_t rem = min(64u, total - c0);
+                        MCMC_DRAIN_CHUNK(cur, rem, rowfull);
+                        if (rowfull) break;
                     }
                 }
-#pragma unroll
-                for (int j = 0; j < 4; j++) m[j] = or_xor64(or_xor64(m[j], 16), 32);
-                bool mine = true;
-#pragma unroll
-                for (int j = 0; j < 4; j++) mine = mine && (m[j] == full || ((dead4 >> j) & 1u));
-                if (__all(mine)) break;
+                if (++rg == a.grp_rows) {
+                    rg = 0u;
+                    grp++;
+                }
             }
             // chain `lane`: word lane & 3 of lane lane >> 2
             const int src = (int)(lane >> 2);
@@ -312,6 +408,8 @@ struct mcmc_chains {
     const mcmc_graph* g = nullptr;
     mcmc_params p{};
     ChainArgs a{};
+    bool tiled = false;           // the sweep reads the graph's tiled layout (no CSR), else the CSR
+    size_t bytes = 0;             // of `mem`
     void* mem = nullptr;          // one device allocation behind every pointer of `a`
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -324,6 +422,11 @@ struct mcmc_chains {
 };
 
 namespace {
+
+// workgroups of a sweep along x: kSweepWaves waves of vb vertices each
+uint32_t chains_grid_x(const ChainArgs& a) {
+    return (uint32_t)(((uint64_t)a.n + (uint64_t)a.vb * kSweepWaves - 1) / ((uint64_t)a.vb * kSweepWaves));
+}
 
 int chains_sync_state(mcmc_chains* c) {
     c->st.resize(c->a.R);
@@ -362,9 +465,17 @@ int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mc
         return fail(MCMC_E_ARG, "chains: 2 <= nCol <= 64 (one 64-bit occupancy mask per lane), got " + std::to_string(p->nCol));
     if (R < 1 || R > kMaxChains) return fail(MCMC_E_ARG, "chains: 1 <= R <= 1024, got " + std::to_string(R));
     if (gd.n == 0) return fail(MCMC_E_ARG, "chains: empty graph");
-    if (!gd.row_off || gd.partial_rows)
-        return fail(MCMC_E_ARG, "chains: the graph needs a whole device CSR (mcmc_graph_upload / _simulate / _rmat, or "
-                                "mcmc_graph_materialize_csr after mcmc_graph_er_fast)");
+    if (gd.partial_rows)
+        return fail(MCMC_E_ARG, "chains: the graph holds a row range only (mcmc_graph_er_fast_rows / _part); a batch "
+                                "needs every row");
+    const TiledLayout* L = nullptr;   // a generated graph: its full-range layout, read as it is
+    if (!gd.row_off) {
+        for (auto& tl : g->tiles)
+            if (tl->v_begin == 0 && tl->v_end == gd.n) L = tl.get();
+        if (!L)
+            return fail(MCMC_E_ARG, "chains: the graph has neither a whole device CSR (mcmc_graph_upload / _simulate / "
+                                    "_rmat) nor a full-range tiled layout (mcmc_graph_er_fast)");
+    }
     MCMC_HIP_TRY(hipSetDevice(gd.device));
     const uint32_t n = gd.n, G = (R + kLanes - 1) / kLanes, RP = G * kLanes;
     const uint32_t traj_cap = (uint32_t)std::min<uint64_t>((uint64_t)p->maxRip + 2u, kTrajCapMax);
@@ -414,6 +525,16 @@ int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mc
     a.row_off = gd.row_off;
     a.col_idx = gd.col_idx;
     a.m = gd.m;
+    if (L) {
+        a.tcol = L->tcol;
+        a.gbase = L->gbase;
+        a.tseg = L->tseg;
+        a.grp_rows = L->grp_rows;
+        a.nblocks = L->nblocks;
+        a.block_log2 = L->block_log2;
+    }
+    c->tiled = L != nullptr;
+    c->bytes = need;
     a.n = n;
     a.R = R;
     a.G = G;
@@ -450,6 +571,13 @@ int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mc
     return MCMC_OK;
 }
 
+int mcmc_chains_get_info(mcmc_chains* c, uint64_t out[8]) {
+    if (!c || !out) return fail(MCMC_E_ARG, "NULL argument");
+    const uint64_t w[8] = {c->tiled ? 1u : 0u, c->bytes, c->a.vb, c->a.G, chains_grid_x(c->a), 0u, 0u, 0u};
+    std::memcpy(out, w, sizeof(w));
+    return MCMC_OK;
+}
+
 int mcmc_chains_set_glibc_windows(mcmc_chains* c, const uint32_t* windows) {
     if (!c || !windows) return fail(MCMC_E_ARG, "NULL argument");
     MCMC_HIP_TRY(hipSetDevice(c->g->g.device));
@@ -482,7 +610,7 @@ int mcmc_chains_run(mcmc_chains* c, uint32_t max_sweeps, mcmc_run_stats* stats) 
     const uint64_t cap = (uint64_t)a.maxRip + 2u;
     const uint64_t left = cap > c->t ? cap - c->t : 0u;
     const uint32_t total = (uint32_t)(max_sweeps ? std::min<uint64_t>(max_sweeps, left) : left);
-    const dim3 grid((uint32_t)(((uint64_t)a.n + (uint64_t)a.vb * kSweepWaves - 1) / ((uint64_t)a.vb * kSweepWaves)), a.G);
+    const dim3 grid(chains_grid_x(a), a.G);
     c->cache_g = -1;
     MCMC_HIP_TRY(hipEventRecord(c->ev0, c->stream));
     // The all-done counter is read every kPollSweeps sweeps: a read drains the stream (~20 us), a
@@ -492,7 +620,10 @@ int mcmc_chains_run(mcmc_chains* c, uint32_t max_sweeps, mcmc_run_stats* stats) 
         const uint32_t b = std::min(kPollSweeps, total - k);
         for (uint32_t j = 0; j < b; j++, c->t++) {
             const uint32_t tn = (uint32_t)(((uint64_t)c->t * a.n) % kMinstdN);
-            chains_sweep_kernel<<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+            if (c->tiled)
+                chains_sweep_kernel<true><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+            else
+                chains_sweep_kernel<false><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
             chains_commit_kernel<<<a.R, 64, 0, c->stream>>>(a, c->t);
         }
         MCMC_HIP_TRY(hipGetLastError());

@@ -311,7 +311,8 @@ int main(int argc, char** argv) {
             sweeps += batch.getStats(r).iter;
         }
         std::cout << "MCMC GPU chains elapsed time: " << batch.getStats(0).loopMs / 1000.0 << " (" << chains
-                  << " chains, " << sweeps << " chain-sweeps)" << std::endl;
+                  << " chains, " << sweeps << " chain-sweeps, rows from the "
+                  << (batch.info()[0] ? "tiled layout" : "CSR") << ")" << std::endl;
         repetitions = 0;
     }
     for (uint32_t i = 0; i < repetitions; i++) {
