@@ -363,6 +363,13 @@ public:
     ColoringMCMCChains(Graph<nodeW, edgeW>* inGraph_d, GPURandHandle* randStates, ColoringMCMCParams params,
                        uint32_t chains)
         : graph(inGraph_d), seed(randStates->seed), param(params), R(chains) {}
+    // A ladder (mcmc_chains_create_ladder): chain r has its own specs[r] = {nCol, seed, epsilon, 0};
+    // params supplies maxRip, tabooIteration and tailcut.
+    ColoringMCMCChains(Graph<nodeW, edgeW>* inGraph_d, ColoringMCMCParams params, std::vector<mcmc_chain_spec> ladder)
+        : graph(inGraph_d), seed(ladder.empty() ? 0u : ladder[0].seed), param(params), R((uint32_t)ladder.size()),
+          specs(std::move(ladder)) {}
+    ColoringMCMCChains(const ColoringMCMCChains&) = delete;
+    ColoringMCMCChains& operator=(const ColoringMCMCChains&) = delete;
     ~ColoringMCMCChains() { mcmc_chains_destroy(ctx); }
 
     void run() {
@@ -378,7 +385,10 @@ public:
         p.tabooIteration = param.tabooIteration;
         p.tailcut = param.tailcut;
         p.seed = seed;
-        MCMC_CHECK(mcmc_chains_create(graph->handle(), &p, R, &ctx));   // a generated graph: its tiled layout, no CSR
+        if (specs.empty())
+            MCMC_CHECK(mcmc_chains_create(graph->handle(), &p, R, &ctx));   // a generated graph: its tiled layout, no CSR
+        else
+            MCMC_CHECK(mcmc_chains_create_ladder(graph->handle(), &p, specs.data(), R, &ctx));
         MCMC_CHECK(mcmc_chains_set_tailcut_repair(ctx, param.tailcutRepair));
         std::vector<uint32_t> w((size_t)R * 31);
         for (uint32_t r = 0; r < R; r++) std::memcpy(&w[(size_t)r * 31], mcmc::glibc_global().w, 31 * sizeof(uint32_t));
@@ -398,6 +408,50 @@ public:
         return w;
     }
     const mcmc_run_stats& getStats(uint32_t r) const { return stats.at(r); }
+    // chain r's nCol, seed and epsilon
+    mcmc_chain_spec spec(uint32_t r) const {
+        return specs.empty() ? mcmc_chain_spec{param.nCol, seed + r, param.epsilon, 0u} : specs.at(r);
+    }
+    // [chains][64] class sizes of every chain's colouring, counted on the device
+    std::vector<uint32_t> histograms() const {
+        std::vector<uint32_t> h((size_t)R * 64);
+        MCMC_CHECK(mcmc_chains_get_histograms(ctx, h.data()));
+        return h;
+    }
+    // One line per chain (nCol, epsilon, seed, iter, maxIterReached, finalViol, used colours, min / max
+    // class size, deviation of the class sizes over nCol) and the index of the chain to keep: among
+    // the converged ones the smallest nCol, then the smallest deviation, then the lowest index; -1 if
+    // none converged. Host code over the device histograms.
+    int summary(std::ostream& out) const {
+        const std::vector<uint32_t> h = histograms();
+        int best = -1;
+        double bestStd = 0;
+        for (uint32_t r = 0; r < R; r++) {
+            const mcmc_chain_spec sp = spec(r);
+            const mcmc_run_stats& st = stats.at(r);
+            uint32_t used = 0, mn = ~0u, mx = 0;
+            double mean = 0, var = 0;
+            for (uint32_t k = 0; k < sp.nCol; k++) {
+                const uint32_t x = h[(size_t)r * 64 + k];
+                used += x ? 1 : 0;
+                mn = std::min(mn, x);
+                mx = std::max(mx, x);
+                mean += x;
+            }
+            mean /= sp.nCol;
+            for (uint32_t k = 0; k < sp.nCol; k++) var += (h[(size_t)r * 64 + k] - mean) * (h[(size_t)r * 64 + k] - mean);
+            const double sd = std::sqrt(var / sp.nCol);
+            out << "chain " << r << ": nCol " << sp.nCol << " epsilon " << sp.epsilon << " seed " << sp.seed << " iter "
+                << st.iter << " maxIterReached " << st.maxIterReached << " finalViol " << st.finalViol << " used " << used
+                << " min " << mn << " max " << mx << " std " << sd << std::endl;
+            if (!st.maxIterReached &&
+                (best < 0 || sp.nCol < spec(best).nCol || (sp.nCol == spec(best).nCol && sd < bestStd))) {
+                best = (int)r;
+                bestStd = sd;
+            }
+        }
+        return best;
+    }
     std::vector<uint32_t> getColoring(uint32_t r) const {
         std::vector<uint32_t> c(graph->getNNodes());
         MCMC_CHECK(mcmc_chains_get_coloring(ctx, r, c.data()));
@@ -416,7 +470,7 @@ public:
         const std::vector<uint64_t> trajectory = getTrajectory(r);
         const mcmc_run_stats& st = stats.at(r);
         std::ofstream out(directory + ".log");
-        const uint32_t nCol = param.nCol;
+        const uint32_t nCol = spec(r).nCol;
         out << "MCMC Colorer - GPU (MI355X) version - Report" << std::endl;
         out << "-------------------------------------------" << std::endl;
         out << "GRAPH INFO" << std::endl;
@@ -424,7 +478,7 @@ public:
         out << "Max deg: " << graph->getMaxNodeDeg() << " - Min deg: " << graph->getMinNodeDeg()
             << " - Avg deg: " << graph->getMeanNodeDeg() << std::endl;
         out << "Edge probability (for randomly generated graphs): " << graph->prob << std::endl;
-        out << "Seed: " << seed + r << std::endl;
+        out << "Seed: " << spec(r).seed << std::endl;
         out << "-------------------------------------------" << std::endl;
         out << "EXECUTION INFO" << std::endl;
         out << "Repetition: " << r << std::endl;
@@ -460,6 +514,7 @@ private:
     uint32_t seed;
     ColoringMCMCParams param;
     uint32_t R;
+    std::vector<mcmc_chain_spec> specs;   // a ladder's; empty: uniform
     mcmc_chains* ctx{nullptr};
     std::vector<mcmc_run_stats> stats;
 };

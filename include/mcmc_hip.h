@@ -271,8 +271,20 @@ void mcmc_destroy(mcmc_ctx* c);
 typedef struct mcmc_chains mcmc_chains;
 /* params.seed is chain 0's seed. Draws every chain's initial colouring (mcmc_init_coloring's). */
 int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mcmc_chains** out);
+/* A ladder: chain r has its own nCol, epsilon and engine seed (specs[r]), so one full-width batch
+ * answers "the smallest nCol that still converges within maxRip, at which epsilon" where the uniform
+ * batch needs one small batch per (nCol, epsilon) pair. Chain r is, bit for bit,
+ * ColoringMCMC_CPU(g, {specs[r].nCol, specs[r].epsilon, ...}, specs[r].seed).run(). `p` supplies
+ * maxRip, tabooIteration and tailcut; its nCol, seed and epsilon are ignored. Every spec needs
+ * 2 <= nCol <= 64 and reserved == 0, else MCMC_E_ARG naming the chain; the graph rules are those of
+ * mcmc_chains_create, and every other mcmc_chains_* call works on the result. The sweep is the
+ * ladder instantiation of the kernel (per-lane nCol and epsilon) also when all specs are equal. */
+typedef struct { uint32_t nCol, seed; float epsilon; uint32_t reserved; } mcmc_chain_spec;
+int mcmc_chains_create_ladder(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_spec* specs, uint32_t R,
+                              mcmc_chains** out);
 /* out[0] adjacency source of the sweep (0 CSR, 1 tiled layout), [1] device bytes of the batch's own
- * allocation, [2] vertices per wave, [3] chain groups, [4] sweep grid x, [5..7] 0. */
+ * allocation, [2] vertices per wave, [3] chain groups, [4] sweep grid x, [5] 1 for a ladder
+ * (mcmc_chains_create_ladder), else 0, [6..7] 0. */
 int mcmc_chains_get_info(mcmc_chains* c, uint64_t out[8]);
 /* windows[R][31]; default: every chain at srand(1) with no draws (mcmc_set_glibc_window's default).
  * mcmc_chains_get_glibc_windows returns them advanced by each chain's glibcDraws. */
@@ -286,6 +298,11 @@ int mcmc_chains_set_tailcut_repair(mcmc_chains* c, uint32_t max_passes);
  * continues). stats[R] (may be NULL): per chain, loopMs = the batch's device time (hipEvent). */
 int mcmc_chains_run(mcmc_chains* c, uint32_t max_sweeps, mcmc_run_stats* stats /* R */);
 int mcmc_chains_get_coloring(mcmc_chains* c, uint32_t r, uint32_t* out /* n */);
+/* Class sizes on the device: out[r][k] = vertices of colour k in chain r's colouring as
+ * mcmc_chains_get_coloring returns it (k >= the chain's nCol: 0). One kernel over the colour bytes,
+ * R x 64 words copied back; computed on demand and kept until the next mcmc_chains_run. Both kinds
+ * of batch. */
+int mcmc_chains_get_histograms(mcmc_chains* c, uint32_t* out /* [R][64] */);
 int mcmc_chains_get_trajectory(mcmc_chains* c, uint32_t r, uint64_t* out, uint64_t cap, uint64_t* len);
 void mcmc_chains_destroy(mcmc_chains* c);
 

@@ -65,6 +65,8 @@ SIGNATURES: dict[str, tuple] = {
     "mcmc_refstruct_bench": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32, POINTER(c_double), _u64p]),
     "mcmc_destroy": (None, [c_void_p]),
     "mcmc_chains_create": (c_int, [c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
+    "mcmc_chains_create_ladder": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
+    "mcmc_chains_get_histograms": (c_int, [c_void_p, _u32p]),
     "mcmc_chains_get_info": (c_int, [c_void_p, _u64p]),
     "mcmc_chains_set_glibc_windows": (c_int, [c_void_p, _u32p]),
     "mcmc_chains_get_glibc_windows": (c_int, [c_void_p, _u32p]),
@@ -125,6 +127,12 @@ class MCMCParams(ctypes.Structure):
         ("tailcut", c_int32),
         ("seed", c_uint32),
     ]
+
+
+class MCMCChainSpec(ctypes.Structure):
+    """mcmc_chain_spec: one chain of a ladder (mcmc_chains_create_ladder)."""
+
+    _fields_ = [("nCol", c_uint32), ("seed", c_uint32), ("epsilon", c_float), ("reserved", c_uint32)]
 
 
 class MCMCRunStats(ctypes.Structure):

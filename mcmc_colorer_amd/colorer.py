@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import MCMCCtxInfo, MCMCParams, MCMCRunStats, check, lib, u32ptr, u64ptr
+from ._lib import MCMCChainSpec, MCMCCtxInfo, MCMCParams, MCMCRunStats, check, lib, u32ptr, u64ptr
 
 F32_EPS = float(np.float32(1e-8))
 
@@ -363,20 +363,38 @@ class ColoringMCMCChains:
     whose position every chain starts at, or a list of ``chains`` of them; advanced in place by
     ``run()``), where ``ColoringMCMC.run(i + 1)`` continues the stream ``run(i)`` left. 2 <= nCol <= 64,
     1 <= chains <= 1024, a graph with a device CSR or a whole ``Graph.er_fast`` graph, whose tiled
-    16-bit layout the sweep reads as it is (no CSR is built); no tail-cut repair."""
+    16-bit layout the sweep reads as it is (no CSR is built); no tail-cut repair.
+    ``ColoringMCMCChains.ladder`` gives every chain its own nCol, epsilon and seed; ``histograms()``,
+    ``summary()`` and ``best()`` compare the chains from class sizes counted on the device."""
 
-    def __init__(self, graph: Graph, params: ColoringMCMCParams, seed: int, chains: int, glibc=None):
-        if params.nCol == 0:
+    def __init__(self, graph: Graph, params: ColoringMCMCParams, seed: int, chains: int, glibc=None, specs=None):
+        if params.nCol == 0 and specs is None:
             params = ColoringMCMCParams(**{**params.__dict__, "nCol": default_ncol(graph, params)})
         self.graph, self.param, self.seed, self.chains = graph, params, seed, int(chains)
         self._h = ctypes.c_void_p()
         self._cparams = params.to_c(seed)
-        check(lib().mcmc_chains_create(graph.handle, ctypes.byref(self._cparams), self.chains, ctypes.byref(self._h)))
+        if specs is None:   # uniform: every chain params.nCol, params.epsilon, seed + r
+            self.specs = [(params.nCol, float(np.float32(params.epsilon)), (seed + r) & 0xFFFFFFFF)
+                          for r in range(self.chains)]
+            check(lib().mcmc_chains_create(graph.handle, ctypes.byref(self._cparams), self.chains, ctypes.byref(self._h)))
+        else:
+            self.specs = [(int(k), float(np.float32(e)), int(s) & 0xFFFFFFFF) for k, e, s in specs]
+            arr = (MCMCChainSpec * self.chains)(*[MCMCChainSpec(k, s, e, 0) for k, e, s in self.specs])
+            check(lib().mcmc_chains_create_ladder(graph.handle, ctypes.byref(self._cparams), arr, self.chains,
+                                                  ctypes.byref(self._h)))
         check(lib().mcmc_chains_set_tailcut_repair(self._h, int(params.tailcutRepair)))
         if glibc is None:
             glibc = GlibcRand(1)
         self.glibc = [glibc] * self.chains if isinstance(glibc, GlibcRand) else list(glibc)
         self._stats: list[MCMCRunStats] = []
+
+    @classmethod
+    def ladder(cls, graph: Graph, params: ColoringMCMCParams, specs, glibc=None) -> "ColoringMCMCChains":
+        """One batch whose chain r has its own ``specs[r] = (nCol, epsilon, seed)`` (2 <= nCol <= 64):
+        mcmc_chains_create_ladder. ``params`` supplies maxRip, tabooIteration and tailcut; its nCol and
+        epsilon are ignored. Chain r equals the single run with its own three values, bit for bit."""
+        specs = list(specs)
+        return cls(graph, params, specs[0][2] if specs else 0, len(specs), glibc=glibc, specs=specs)
 
     def run(self, max_sweeps: int = 0) -> list[MCMCRunStats]:
         w = np.ascontiguousarray(np.stack([g.window for g in self.glibc]), dtype=np.uint32)
@@ -395,10 +413,35 @@ class ColoringMCMCChains:
 
     def info(self) -> list[int]:
         """mcmc_chains_get_info: [adjacency source (0 CSR, 1 tiled layout), device bytes of the batch,
-        vertices per wave, chain groups, sweep grid x, 0, 0, 0]."""
+        vertices per wave, chain groups, sweep grid x, 1 for a ladder, 0, 0]."""
         out = np.zeros(8, dtype=np.uint64)
         check(lib().mcmc_chains_get_info(self._h, u64ptr(out)))
         return [int(x) for x in out]
+
+    def histograms(self) -> np.ndarray:
+        """[chains][64] class sizes of every chain's colouring, counted on the device
+        (mcmc_chains_get_histograms): no colouring is copied to the host."""
+        out = np.zeros((self.chains, 64), dtype=np.uint32)
+        check(lib().mcmc_chains_get_histograms(self._h, u32ptr(out)))
+        return out
+
+    def summary(self) -> list[dict]:
+        """Per chain, after run(): nCol, epsilon, seed, iter, maxIterReached, finalViol, used colours,
+        min / max class size and the standard deviation of the class sizes over nCol."""
+        hist = self.histograms()
+        res = []
+        for r, ((k, e, s), st) in enumerate(zip(self.specs, self._stats)):
+            h = hist[r, :k].astype(np.float64)
+            res.append({"chain": r, "nCol": k, "epsilon": e, "seed": s, "iter": st.iter,
+                        "maxIterReached": int(st.maxIterReached), "finalViol": st.finalViol,
+                        "used": int((h > 0).sum()), "min": int(h.min()), "max": int(h.max()), "std": float(h.std())})
+        return res
+
+    def best(self):
+        """The summary row of the chain to keep: among those that converged (maxIterReached == 0) the
+        smallest nCol, then the smallest deviation, then the lowest index; None if none converged."""
+        ok = [d for d in self.summary() if d["maxIterReached"] == 0]
+        return min(ok, key=lambda d: (d["nCol"], d["std"], d["chain"])) if ok else None
 
     def colorings(self) -> np.ndarray:
         out = np.zeros((self.chains, self.graph.nNodes), dtype=np.uint32)

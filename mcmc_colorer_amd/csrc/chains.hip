@@ -50,9 +50,23 @@
 //   the chain's overflow records in ascending vertex order (wave min-scan of the group's list per
 //   event -- events are ~1e-7 per draw) from the chain's glibc window: colour rand() % (nCol - 1)
 //   and the taboo value (:518-526). The last chain to stop makes later launches return at once.
-// Init (chains_init_kernel): one lane per chain walks default_random_engine(seed + r) through
-//   uniform_int_distribution(0, nCol - 1) in vertex order, rejections included (:53-61), so
-//   initDraws differs per chain and is exact without a host replay.
+// Init (chains_init_kernel): one lane per chain walks default_random_engine(seed_r) through
+//   uniform_int_distribution(0, nCol_r - 1) in vertex order, rejections included (:53-61), so
+//   initDraws differs per chain and is exact without a host replay. seed_r and the distribution's
+//   constants come from a per-chain table the host builds.
+// Ladder (mcmc_chains_create_ladder): chain r has its own nCol_r, eps_r and seed_r. The sweep's
+//   LADDER instantiations (CSR and tiled) read nCol and epsilon per lane; the uniform instantiations
+//   are the code objects they were (63 / 70 and 67 / 91 VGPRs / SGPRs, no scratch). A lane's four
+//   partial masks belong to four chains of four widths: their nCol travel as four bytes of one
+//   VGPR, every mask starts at the complement of its chain's colour set (all ones when the chain is
+//   not live), and "every live mask full" is "all four all ones" whatever the widths. The update
+//   takes mask & full_lane; hi, fr, ps and the walk's "not found" value are the lane's own; the walk
+//   runs to the wave's largest live nCol (one wave reduction per block), a lane adding and testing
+//   only while k < nCol_l, in the same fp32 order as the single run. The commit draws
+//   rand() % (nCol_r - 1).
+// Histograms (chains_hist_kernel): hist[r][k] = vertices of colour k in chain r's final colouring,
+//   read from the buffer each chain stopped in (selected per byte of the drain's dword), counted in
+//   an LDS table [64 chains][64 colours], one global atomic per nonzero cell and workgroup.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -102,6 +116,11 @@ struct ChainArgs {
     uint32_t* ring;         // [G * 64][31] glibc windows as rings
     uint32_t* traj;         // [R][traj_cap]
     uint32_t* ndone;        // chains that stopped
+    // per chain (a ladder's differ; a uniform batch holds nCol, eps in every entry): the ladder
+    // instantiations of the sweep, the commit's rand() % (nCol_r - 1)
+    const uint8_t* ncol;    // [G * 64], 0 past R
+    const float* epsr;      // [G * 64]
+    uint32_t* hist;         // [G * 64][64] class sizes of the final colourings (chains_hist_kernel)
 };
 
 __device__ __forceinline__ uint64_t shfl64(uint64_t x, int src) {
@@ -137,7 +156,10 @@ __device__ __forceinline__ void drain_steps(const uint32_t* __restrict__ Cw, uin
 // One chunk of the drain, shared by the CSR and the tiled instantiation: the 4-neighbour steps over
 // the `rem` ids of `cur`, the OR-reduction of the partial masks over the four quarters, and the exit
 // test -- `all_full`: every live chain's mask is full. A macro, not a function: through a function
-// (forced inline) the CSR sweep compiled to 81 VGPRs instead of 63.
+// (forced inline) the CSR sweep compiled to 81 VGPRs instead of 63. Ladder: a mask starts at the
+// complement of its chain's own colour set (all ones for a chain that is not live), so "full" is all
+// ones for every width; the test is skipped while fewer neighbours are drained than the smallest
+// live nCol of the wave (it cannot succeed).
 #define MCMC_DRAIN_CHUNK(cur, rem, all_full)                                                        \
     do {                                                                                            \
         for (uint32_t s = 0; 4u * s < (rem);) {                                                     \
@@ -150,10 +172,15 @@ __device__ __forceinline__ void drain_steps(const uint32_t* __restrict__ Cw, uin
             }                                                                                       \
         }                                                                                           \
         _Pragma("unroll") for (int j = 0; j < 4; j++) m[j] = or_xor64(or_xor64(m[j], 16), 32);      \
-        bool mine = true;                                                                           \
-        _Pragma("unroll") for (int j = 0; j < 4; j++)                                               \
-            mine = mine && (m[j] == full || ((dead4 >> j) & 1u));                                   \
-        all_full = __all(mine);                                                                     \
+        if constexpr (LADDER) {                                                                     \
+            drained += (rem);                                                                       \
+            all_full = drained >= nmin && __all((m[0] & m[1] & m[2] & m[3]) == ~0ull);              \
+        } else {                                                                                    \
+            bool mine = true;                                                                       \
+            _Pragma("unroll") for (int j = 0; j < 4; j++)                                           \
+                mine = mine && (m[j] == full || ((dead4 >> j) & 1u));                               \
+            all_full = __all(mine);                                                                 \
+        }                                                                                           \
     } while (0)
 
 // Tiled layout: the ids of slots c0 .. c0 + 63 of a directory round's flattened stream (lane j: slot
@@ -175,7 +202,11 @@ __device__ __forceinline__ uint32_t tiled_chunk(const uint16_t* __restrict__ ids
 }
 
 // TILED = false: the rows come from the CSR; true: from the full-range tiled layout.
-template <bool TILED>
+// LADDER = false: one nCol and epsilon for the batch (kernel arguments, wave-uniform); true: chain r
+// has its own nCol_r, eps_r (a.ncol, a.epsr). What differs: the masks' start values and the exit test
+// (MCMC_DRAIN_CHUNK), and in the update full, hi, fr, ps and the walk's end are per lane; the walk
+// runs to the wave's largest live nCol, a lane adding and testing only while k < nCol_l.
+template <bool TILED, bool LADDER>
 __global__ __launch_bounds__(64 * kSweepWaves) void chains_sweep_kernel(ChainArgs a, uint32_t t, uint32_t tn) {
     if (*a.ndone >= a.R) return;   // every chain stopped (workgroup-uniform)
     __shared__ uint32_t s_viol[kLanes];
@@ -200,6 +231,29 @@ __global__ __launch_bounds__(64 * kSweepWaves) void chains_sweep_kernel(ChainArg
         // the four chains this lane's partial masks belong to that are not live count as full
         const uint32_t dead4 = ~(uint32_t)(livemask >> (4u * i)) & 15u;
         const float eps = a.eps, hi = 1.0f - (float)(nCol - 1u) * eps;   // :402-412, :471-479
+        // ladder: this lane's chain (nl, el, hl, fulll), the four chains of its partial masks (nc4: their
+        // nCol as bytes, 0 where not live), the wave's smallest and largest live nCol
+        uint32_t nl = 0u, nc4 = 0u, nmin = 0u, nmax = 0u;
+        float el = 0.0f, hl = 0.0f;
+        uint64_t fulll = 0ull;
+        if constexpr (LADDER) {
+            nl = a.ncol[r];
+            el = a.epsr[r];
+            hl = 1.0f - (float)(nl - 1u) * el;
+            fulll = nl == 64u ? ~0ull : (1ull << nl) - 1ull;
+            nc4 = reinterpret_cast<const uint32_t*>(a.ncol)[g * 16u + i];
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if ((dead4 >> j) & 1u) nc4 &= ~(255u << (8 * j));
+            uint32_t lo = live ? nl : 64u, hx = live ? nl : 0u;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                lo = min(lo, (uint32_t)__shfl_xor((int)lo, o, 64));
+                hx = max(hx, (uint32_t)__shfl_xor((int)hx, o, 64));
+            }
+            nmin = (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+            nmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)hx);
+        }
         // engine state of the block's first vertex: x_r 16807^(t n + v0 + 1)
         uint64_t e = (uint64_t)tn + v0 + 1ull;
         while (e >= kMinstdN) e -= kMinstdN;
@@ -215,6 +269,14 @@ __global__ __launch_bounds__(64 * kSweepWaves) void chains_sweep_kernel(ChainArg
         }
         for (uint32_t v = v0; v < v1; v++) {
             uint64_t m[4] = {0ull, 0ull, 0ull, 0ull};
+            uint32_t drained = 0u;
+            if constexpr (LADDER) {
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const uint32_t b = (nc4 >> (8 * j)) & 255u;
+                    m[j] = b >= 64u ? 0ull : ~0ull << b;
+                }
+            }
             if constexpr (!TILED) {
                 const uint64_t end = min(a.row_off[v + 1], a.m), base = min(a.row_off[v], end);
                 const uint64_t deg = end - base;
@@ -270,34 +332,62 @@ __global__ __launch_bounds__(64 * kSweepWaves) void chains_sweep_kernel(ChainArg
             const int src = (int)(lane >> 2);
             const uint64_t t0 = shfl64(m[0], src), t1 = shfl64(m[1], src), t2 = shfl64(m[2], src), t3 = shfl64(m[3], src);
             const uint32_t jj = lane & 3u;
-            const uint64_t mask = (jj == 0u ? t0 : jj == 1u ? t1 : jj == 2u ? t2 : t3) & full;
+            const uint64_t mask = (jj == 0u ? t0 : jj == 1u ? t1 : jj == 2u ? t2 : t3) & (LADDER ? fulll : full);
             const uint32_t c = Cb[(size_t)v * kLanes + lane];
             const bool viol = (mask >> c) & 1ull;
             nviol += (live && viol) ? 1u : 0u;
-            const uint32_t Zv = (uint32_t)__popcll(mask), fr = nCol - Zv;
+            const uint32_t Zv = (uint32_t)__popcll(mask);
             uint32_t tb = tab ? tab[(size_t)v * kLanes + lane] : 0u;
             uint32_t newc = c;
             bool ovf = false;
             const bool walk = live && tb == 0u;
-            if (__any(walk)) {
-                const float u = minstd_canonical(x);
-                const bool own = !viol || fr == 0u;
-                const uint64_t S = own ? (1ull << c) : ~mask;   // colours whose p is ps; eps elsewhere
-                const float ps = own ? hi : (1.0f - eps * (float)Zv) / (float)fr;
-                float cdf = 0.0f;
-                uint32_t idx = nCol;
-                for (uint32_t k0 = 0; k0 < nCol; k0 += 8u) {
-                    const uint32_t k1 = min(k0 + 8u, nCol);
-                    for (uint32_t k = k0; k < k1; k++) {
-                        cdf += ((S >> k) & 1ull) ? ps : eps;
-                        if (idx == nCol && cdf > u) idx = k;   // strict >, the first colour only (:510-514)
+            if constexpr (!LADDER) {
+                const uint32_t fr = nCol - Zv;
+                if (__any(walk)) {
+                    const float u = minstd_canonical(x);
+                    const bool own = !viol || fr == 0u;
+                    const uint64_t S = own ? (1ull << c) : ~mask;   // colours whose p is ps; eps elsewhere
+                    const float ps = own ? hi : (1.0f - eps * (float)Zv) / (float)fr;
+                    float cdf = 0.0f;
+                    uint32_t idx = nCol;
+                    for (uint32_t k0 = 0; k0 < nCol; k0 += 8u) {
+                        const uint32_t k1 = min(k0 + 8u, nCol);
+                        for (uint32_t k = k0; k < k1; k++) {
+                            cdf += ((S >> k) & 1ull) ? ps : eps;
+                            if (idx == nCol && cdf > u) idx = k;   // strict >, the first colour only (:510-514)
+                        }
+                        if (__all(!walk || idx != nCol)) break;
                     }
-                    if (__all(!walk || idx != nCol)) break;
+                    if (walk) {
+                        ovf = idx == nCol;
+                        newc = ovf ? c : idx;
+                        tb = (newc == c) ? a.taboo_it : 0u;   // :526 (an overflow's is written by the commit)
+                    }
                 }
-                if (walk) {
-                    ovf = idx == nCol;
-                    newc = ovf ? c : idx;
-                    tb = (newc == c) ? a.taboo_it : 0u;   // :526 (an overflow's is written by the commit)
+            } else {
+                const uint32_t fr = nl - Zv;
+                if (__any(walk)) {
+                    const float u = minstd_canonical(x);
+                    const bool own = !viol || fr == 0u;
+                    const uint64_t S = own ? (1ull << c) : ~mask;
+                    const float ps = own ? hl : (1.0f - el * (float)Zv) / (float)fr;
+                    float cdf = 0.0f;
+                    uint32_t idx = nl;   // "not found" is the chain's own nCol: an overflow exactly when its oracle has one
+                    for (uint32_t k0 = 0; k0 < nmax; k0 += 8u) {
+                        const uint32_t k1 = min(k0 + 8u, nmax);
+                        for (uint32_t k = k0; k < k1; k++) {
+                            if (k < nl) {
+                                cdf += ((S >> k) & 1ull) ? ps : el;
+                                if (idx == nl && cdf > u) idx = k;
+                            }
+                        }
+                        if (__all(!walk || idx != nl || k1 >= nl)) break;
+                    }
+                    if (walk) {
+                        ovf = idx == nl;
+                        newc = ovf ? c : idx;
+                        tb = (newc == c) ? a.taboo_it : 0u;
+                    }
                 }
             }
             if (live && !walk) tb--;   // :496-501
@@ -360,7 +450,7 @@ __global__ __launch_bounds__(64) void chains_commit_kernel(ChainArgs a, uint32_t
         for (int o = 32; o > 0; o >>= 1) best = min(best, (uint32_t)__shfl_xor((int)best, o, 64));
         if (best == 0xFFFFFFFFu) break;
         if (lane == 0u) {
-            const uint32_t nc = glibc_next(ring, head) % (a.nCol - 1u);   // :518
+            const uint32_t nc = glibc_next(ring, head) % ((uint32_t)a.ncol[r] - 1u);   // :518, the chain's own nCol
             const size_t at = (size_t)best * kLanes + bit;
             Cn[at] = (uint8_t)nc;
             if (a.taboo) a.taboo[gofs + at] = (nc == Cc[at]) ? a.taboo_it : 0u;   // :526
@@ -376,11 +466,16 @@ __global__ __launch_bounds__(64) void chains_commit_kernel(ChainArgs a, uint32_t
     }
 }
 
-__global__ __launch_bounds__(64) void chains_init_kernel(ChainArgs a, uint32_t seed0, UniformIntConst k) {
+// tab[G * 64]: {the chain's engine seed, its UniformIntConst scaling and past, 0}, built by the host
+__global__ __launch_bounds__(64) void chains_init_kernel(ChainArgs a, const uint4* __restrict__ tab) {
     const uint32_t lane = threadIdx.x, g = blockIdx.x, r = g * kLanes + lane;
     const bool live = r < a.R;
     uint8_t* C0 = a.C[0] + (size_t)g * a.n * kLanes;
-    uint32_t x = minstd_seed_state(seed0 + r);
+    const uint4 sp = tab[r];
+    UniformIntConst k;
+    k.scaling = sp.y;
+    k.past = sp.z;
+    uint32_t x = minstd_seed_state(sp.x);
     uint64_t draws = 0;
     for (uint32_t v = 0; v < a.n; v++) {
         uint32_t col = 0u;
@@ -399,6 +494,71 @@ __global__ __launch_bounds__(64) void chains_init_kernel(ChainArgs a, uint32_t s
     a.init_draws[r] = draws;
 }
 
+constexpr uint32_t kHistWaves = 4;   // waves per histogram workgroup
+
+// Class sizes: hist[r][k] = vertices of colour k in chain r's final colouring. Grid (vertex chunks of
+// `hv`, group). Colours are read as the drain reads them: lane l the dword of chains 4 (l & 15) .. +3
+// of vertex l >> 4 of the wave's four, 256 B per wave-load, eight loads in flight. The chains of a
+// group stop at different parities, so a lane's four chains may live in different buffers: sel has
+// 0xFF in the bytes of the chains whose colouring is in buffer 1 (st[r].buf; t & 1 for a chain still
+// running), and a lane loads from the buffers its chains need and merges by byte. Counts go to an LDS
+// table [64 chains][64 colours] with ds_add, then one global atomic per nonzero cell and workgroup.
+// The column is rotated by the chain so that the lanes of a quarter (16 chains x 4, mostly few
+// distinct colours when nCol is small) spread over the banks.
+__global__ __launch_bounds__(64 * kHistWaves) void chains_hist_kernel(ChainArgs a, uint32_t t, uint32_t hv) {
+    __shared__ uint32_t s_h[kLanes * 64u];
+    const uint32_t lane = threadIdx.x & 63u, q = lane >> 4, i = lane & 15u, wid = threadIdx.x >> 6;
+    const uint32_t g = blockIdx.y, n = a.n;
+    for (uint32_t k = threadIdx.x; k < kLanes * 64u; k += 64u * kHistWaves) s_h[k] = 0u;
+    __syncthreads();
+    uint32_t sel = 0u, valid = 0u, vbytes = 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; j++) {
+        const uint32_t r = g * kLanes + 4u * i + j;
+        if (r < a.R) {
+            valid |= 1u << j;
+            vbytes |= 255u << (8u * j);
+            const uint32_t buf = a.st[r].done ? a.st[r].buf : (t & 1u);
+            if (buf & 1u) sel |= 255u << (8u * j);
+        }
+    }
+    const uint32_t need1 = sel, need0 = vbytes & ~sel;
+    const size_t gofs = (size_t)g * n * kLanes;
+    const uint32_t* __restrict__ W0 = reinterpret_cast<const uint32_t*>(a.C[0] + gofs);
+    const uint32_t* __restrict__ W1 = reinterpret_cast<const uint32_t*>(a.C[1] + gofs);
+    const uint64_t vb0 = (uint64_t)blockIdx.x * hv;
+    const uint32_t vend = (uint32_t)min((uint64_t)n, vb0 + hv);
+    // a wave takes 32 vertices (8 loads of 4) per turn, the workgroup's waves interleaved
+    for (uint64_t vt = vb0 + 32ull * wid; vt < vend; vt += 32ull * kHistWaves) {
+        uint32_t w[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; k++) {
+            const uint64_t v = vt + 4u * k + q;
+            uint32_t w0 = 0u, w1 = 0u;
+            if (v < vend) {
+                if (need0) w0 = W0[(size_t)v * 16u + i];
+                if (need1) w1 = W1[(size_t)v * 16u + i];
+            }
+            w[k] = (w0 & ~sel) | (w1 & sel);
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; k++) {
+            if (vt + 4u * k + q < vend) {
+#pragma unroll
+                for (uint32_t j = 0; j < 4u; j++) {
+                    const uint32_t ch = 4u * i + j, col = (w[k] >> (8u * j)) & 63u;
+                    if ((valid >> j) & 1u) atomicAdd(&s_h[ch * 64u + ((col + ch) & 63u)], 1u);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < kLanes * 64u; k += 64u * kHistWaves) {
+        const uint32_t cnt = s_h[k], ch = k >> 6, col = ((k & 63u) - ch) & 63u;
+        if (cnt) atomicAdd(&a.hist[((size_t)g * kLanes + ch) * 64u + col], cnt);
+    }
+}
+
 }  // namespace
 }  // namespace mcmc
 
@@ -409,6 +569,9 @@ struct mcmc_chains {
     mcmc_params p{};
     ChainArgs a{};
     bool tiled = false;           // the sweep reads the graph's tiled layout (no CSR), else the CSR
+    bool ladder = false;          // mcmc_chains_create_ladder: the per-chain instantiations of the sweep
+    std::vector<uint32_t> hist;   // get_histograms: [R][64], valid until the next run
+    bool hist_valid = false;
     size_t bytes = 0;             // of `mem`
     void* mem = nullptr;          // one device allocation behind every pointer of `a`
     hipStream_t stream = nullptr;
@@ -455,15 +618,14 @@ int chains_upload_windows(mcmc_chains* c, const uint32_t* w /* [R][31], nullptr:
 
 }  // namespace
 
-extern "C" {
+namespace {
 
-int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mcmc_chains** out) {
-    if (!g || !p || !out) return fail(MCMC_E_ARG, "NULL argument");
-    *out = nullptr;
+// The batch of mcmc_chains_create (specs: nCol, epsilon of `p` and seed + r for every chain; the
+// uniform sweep) and of mcmc_chains_create_ladder (the caller's specs; the ladder sweep). The
+// arguments other than the graph are checked by the callers.
+int chains_create(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_spec* specs, uint32_t R, bool ladder,
+                  mcmc_chains** out) {
     const GraphDev& gd = g->g;
-    if (p->nCol < 2 || p->nCol > 64)
-        return fail(MCMC_E_ARG, "chains: 2 <= nCol <= 64 (one 64-bit occupancy mask per lane), got " + std::to_string(p->nCol));
-    if (R < 1 || R > kMaxChains) return fail(MCMC_E_ARG, "chains: 1 <= R <= 1024, got " + std::to_string(R));
     if (gd.n == 0) return fail(MCMC_E_ARG, "chains: empty graph");
     if (gd.partial_rows)
         return fail(MCMC_E_ARG, "chains: the graph holds a row range only (mcmc_graph_er_fast_rows / _part); a batch "
@@ -482,8 +644,9 @@ int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mc
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t b_col = up((size_t)n * kLanes * G), b_tab = p->tabooIteration ? up(4 * (size_t)n * kLanes * G) : 0;
     const size_t b_ev = up(sizeof(uint4) * (size_t)n * G), b_traj = up(4 * (size_t)R * traj_cap);
+    const size_t b_hist = up(4 * 64 * (size_t)RP);
     const size_t b_small = up(4 * RP) * 2 + up(8 * RP) + up(4 * 1024) + up(8 * G) + up(sizeof(ChainState) * RP) +
-                           up(4 * 31 * (size_t)RP) + 256;
+                           up(4 * 31 * (size_t)RP) + 256 + up(RP) + up(4 * RP) + up(sizeof(uint4) * RP) + b_hist;
     const size_t need = 2 * b_col + b_tab + b_ev + b_traj + b_small;
     size_t fr = 0, tot = 0;
     MCMC_HIP_TRY(hipMemGetInfo(&fr, &tot));
@@ -522,6 +685,12 @@ int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mc
     a.st = reinterpret_cast<ChainState*>(take(sizeof(ChainState) * RP));
     a.ring = reinterpret_cast<uint32_t*>(take(4 * 31 * (size_t)RP));
     a.ndone = reinterpret_cast<uint32_t*>(take(4));
+    uint8_t* d_ncol = take(RP);
+    float* d_eps = reinterpret_cast<float*>(take(4 * RP));
+    uint4* d_itab = reinterpret_cast<uint4*>(take(sizeof(uint4) * RP));
+    a.ncol = d_ncol;
+    a.epsr = d_eps;
+    a.hist = reinterpret_cast<uint32_t*>(take(b_hist));
     a.row_off = gd.row_off;
     a.col_idx = gd.col_idx;
     a.m = gd.m;
@@ -534,6 +703,7 @@ int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mc
         a.block_log2 = L->block_log2;
     }
     c->tiled = L != nullptr;
+    c->ladder = ladder;
     c->bytes = need;
     a.n = n;
     a.R = R;
@@ -554,8 +724,21 @@ int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mc
         for (uint32_t j = 1; j < 256; j++) tab[k * 256 + j] = minstd_mulmod(tab[k * 256 + j - 1], b);
     }
     e = hipMemcpy(powtab, tab.data(), 4096, hipMemcpyHostToDevice);
+    // per-chain tables: nCol, epsilon, and the init kernel's {seed, UniformIntConst}
+    std::vector<uint8_t> h_ncol(RP, 0);
+    std::vector<float> h_eps(RP, 0.0f);
+    std::vector<uint4> h_itab(RP, make_uint4(1u, 1u, 1u, 0u));
+    for (uint32_t r = 0; r < R; r++) {
+        const UniformIntConst k = uniform_int_const(specs[r].nCol);
+        h_ncol[r] = (uint8_t)specs[r].nCol;
+        h_eps[r] = specs[r].epsilon;
+        h_itab[r] = make_uint4(specs[r].seed, k.scaling, k.past, 0u);
+    }
+    if (e == hipSuccess) e = hipMemcpy(d_ncol, h_ncol.data(), RP, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_eps, h_eps.data(), 4 * (size_t)RP, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_itab, h_itab.data(), sizeof(uint4) * (size_t)RP, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        chains_init_kernel<<<G, 64, 0, c->stream>>>(a, p->seed, uniform_int_const(p->nCol));
+        chains_init_kernel<<<G, 64, 0, c->stream>>>(a, d_itab);
         e = hipGetLastError();
     }
     c->init_draws.resize(RP);
@@ -571,9 +754,39 @@ int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mc
     return MCMC_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mcmc_chains** out) {
+    if (!g || !p || !out) return fail(MCMC_E_ARG, "NULL argument");
+    *out = nullptr;
+    if (p->nCol < 2 || p->nCol > 64)
+        return fail(MCMC_E_ARG, "chains: 2 <= nCol <= 64 (one 64-bit occupancy mask per lane), got " + std::to_string(p->nCol));
+    if (R < 1 || R > kMaxChains) return fail(MCMC_E_ARG, "chains: 1 <= R <= 1024, got " + std::to_string(R));
+    std::vector<mcmc_chain_spec> specs(R);
+    for (uint32_t r = 0; r < R; r++) specs[r] = mcmc_chain_spec{p->nCol, p->seed + r, p->epsilon, 0u};
+    return chains_create(g, p, specs.data(), R, false, out);
+}
+
+int mcmc_chains_create_ladder(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_spec* specs, uint32_t R,
+                              mcmc_chains** out) {
+    if (!g || !p || !specs || !out) return fail(MCMC_E_ARG, "NULL argument");
+    *out = nullptr;
+    if (R < 1 || R > kMaxChains) return fail(MCMC_E_ARG, "chains: 1 <= R <= 1024, got " + std::to_string(R));
+    for (uint32_t r = 0; r < R; r++) {
+        if (specs[r].nCol < 2 || specs[r].nCol > 64)
+            return fail(MCMC_E_ARG, "chains: chain " + std::to_string(r) + ": 2 <= nCol <= 64 (one 64-bit occupancy mask "
+                                    "per lane), got " + std::to_string(specs[r].nCol));
+        if (specs[r].reserved != 0)
+            return fail(MCMC_E_ARG, "chains: chain " + std::to_string(r) + ": reserved must be 0");
+    }
+    return chains_create(g, p, specs, R, true, out);
+}
+
 int mcmc_chains_get_info(mcmc_chains* c, uint64_t out[8]) {
     if (!c || !out) return fail(MCMC_E_ARG, "NULL argument");
-    const uint64_t w[8] = {c->tiled ? 1u : 0u, c->bytes, c->a.vb, c->a.G, chains_grid_x(c->a), 0u, 0u, 0u};
+    const uint64_t w[8] = {c->tiled ? 1u : 0u, c->bytes, c->a.vb, c->a.G, chains_grid_x(c->a), c->ladder ? 1u : 0u, 0u, 0u};
     std::memcpy(out, w, sizeof(w));
     return MCMC_OK;
 }
@@ -612,6 +825,7 @@ int mcmc_chains_run(mcmc_chains* c, uint32_t max_sweeps, mcmc_run_stats* stats) 
     const uint32_t total = (uint32_t)(max_sweeps ? std::min<uint64_t>(max_sweeps, left) : left);
     const dim3 grid(chains_grid_x(a), a.G);
     c->cache_g = -1;
+    c->hist_valid = false;
     MCMC_HIP_TRY(hipEventRecord(c->ev0, c->stream));
     // The all-done counter is read every kPollSweeps sweeps: a read drains the stream (~20 us), a
     // sweep + commit pair of a small graph is ~10 us, and the at most kPollSweeps - 1 pairs launched
@@ -620,10 +834,14 @@ int mcmc_chains_run(mcmc_chains* c, uint32_t max_sweeps, mcmc_run_stats* stats) 
         const uint32_t b = std::min(kPollSweeps, total - k);
         for (uint32_t j = 0; j < b; j++, c->t++) {
             const uint32_t tn = (uint32_t)(((uint64_t)c->t * a.n) % kMinstdN);
-            if (c->tiled)
-                chains_sweep_kernel<true><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+            if (c->tiled && c->ladder)
+                chains_sweep_kernel<true, true><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+            else if (c->tiled)
+                chains_sweep_kernel<true, false><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+            else if (c->ladder)
+                chains_sweep_kernel<false, true><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
             else
-                chains_sweep_kernel<false><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+                chains_sweep_kernel<false, false><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
             chains_commit_kernel<<<a.R, 64, 0, c->stream>>>(a, c->t);
         }
         MCMC_HIP_TRY(hipGetLastError());
@@ -672,6 +890,27 @@ int mcmc_chains_get_coloring(mcmc_chains* c, uint32_t r, uint32_t* out) {
         c->cache_buf = buf;
     }
     for (uint32_t v = 0; v < n; v++) out[v] = c->cache[(size_t)v * kLanes + (r % kLanes)];
+    return MCMC_OK;
+}
+
+int mcmc_chains_get_histograms(mcmc_chains* c, uint32_t* out) {
+    if (!c || !out) return fail(MCMC_E_ARG, "NULL argument");
+    MCMC_HIP_TRY(hipSetDevice(c->g->g.device));
+    const ChainArgs& a = c->a;
+    if (!c->hist_valid) {   // computed on demand, kept until the next run
+        // vertices per workgroup: 1024, more once that makes over ~1024 workgroups per group (each
+        // flushes up to 64 x nCol cells); a multiple of the 32 a wave takes per turn
+        const uint32_t hv = (std::max(1024u, (uint32_t)(((uint64_t)a.n + 1023u) / 1024u)) + 31u) & ~31u;
+        const dim3 grid((a.n + hv - 1u) / hv, a.G);
+        MCMC_HIP_TRY(hipMemsetAsync(a.hist, 0, 4 * 64 * (size_t)a.G * kLanes, c->stream));
+        chains_hist_kernel<<<grid, 64 * kHistWaves, 0, c->stream>>>(a, c->t, hv);
+        MCMC_HIP_TRY(hipGetLastError());
+        c->hist.resize((size_t)a.R * 64u);
+        MCMC_HIP_TRY(hipMemcpyAsync(c->hist.data(), a.hist, 4 * c->hist.size(), hipMemcpyDeviceToHost, c->stream));
+        MCMC_HIP_TRY(hipStreamSynchronize(c->stream));
+        c->hist_valid = true;
+    }
+    std::memcpy(out, c->hist.data(), 4 * c->hist.size());
     return MCMC_OK;
 }
 

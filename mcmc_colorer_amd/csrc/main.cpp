@@ -11,6 +11,8 @@
 //   with its inner loop fixed (k++; the reference's never returns), at most 1000 passes
 //   --chains R: with --mcmcgpu, seeds seed .. seed + R - 1 as one batch (csrc/chains.hip), each chain on
 //   its own copy of the glibc stream; writes the files --repet R names
+//   --nColLadder LO:HI: with --chains R (a multiple of K = HI - LO + 1), chain r has nCol LO + r % K and
+//   seed seed + r / K (one batch, the ladder sweep); one summary line per chain and a `best:` line
 // Outputs <outDir>/<graphName>-MCMC_GPU-<i>.log and -colors.txt per repetition.
 // --mcmccpu: ColoringMCMC_CPU's surface (-MCMC_CPU-<i> files, seed + i), run by the same HIP sweep --
 // the CPU colorer's results, bit for bit (the oracle, oracle/build/mcmc_cpu_ref, is test infrastructure);
@@ -125,6 +127,8 @@ void help(const char* argv0) {
               << "  --repet N            repetitions, seeds seed+i (default 1)\n"
               << "  --chains R           --mcmcgpu: seeds seed .. seed+R-1 as ONE batch, a wave lane per chain\n"
               << "                       (nCol <= 64, R <= 1024; each chain its own glibc stream; not with --repet / --gpus)\n"
+              << "  --nColLadder LO:HI   with --chains R, R a multiple of K = HI-LO+1: chain r has nCol LO + r % K and\n"
+              << "                       seed seed + r / K; prints a line per chain and the best one (not with --nCol)\n"
               << "  --seed N             seed (default: time, which also srand()s glibc)\n"
               << "  --outDir D           output directory\n"
               << "  --device D           HIP device (default 0)\n"
@@ -138,7 +142,7 @@ void help(const char* argv0) {
 int main(int argc, char** argv) {
     std::string graphFilename, outDir;
     double prob = 0.0, numColRatio = 0.0;
-    uint32_t n = 0, nCol = 0, seed = 0, repetitions = 1, tabooIteration = 0, chains = 0;
+    uint32_t n = 0, nCol = 0, seed = 0, repetitions = 1, tabooIteration = 0, chains = 0, ladderLo = 0, ladderHi = 0;
     bool repetSet = false;
     bool simulate = false, mcmccpu = false, mcmcgpu = false, tailcut = false, fast = false,
          tailcutRepair = false, mcmcgpuref = false, greedyff = false, lubygpu = false, vffgpu = false;
@@ -157,7 +161,7 @@ int main(int argc, char** argv) {
         {"device", required_argument, 0, 'D'},   {"simulate-fast", required_argument, 0, 'F'},
         {"er-seed", required_argument, 0, 'E'},  {"tailcutRepair", no_argument, 0, 'X'},
         {"mcmcgpu-ref", no_argument, 0, 'G'},    {"gpus", required_argument, 0, 'P'}, {"loopback", no_argument, 0, 'L'},
-        {"chains", required_argument, 0, 'C'},
+        {"chains", required_argument, 0, 'C'},   {"nColLadder", required_argument, 0, 'Y'},
         {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "g:o:s:n:12345k:r:t:lR:S:hD:", longopts, nullptr)) != -1) {
@@ -180,6 +184,15 @@ int main(int argc, char** argv) {
                 case 'l': tailcut = true; break;
                 case 'R': if (std::stoi(optarg) < 1) throw 1; repetitions = std::stoi(optarg); repetSet = true; break;
                 case 'C': if (std::stoi(optarg) < 1) throw 1; chains = std::stoi(optarg); break;
+                case 'Y': {
+                    const std::string a = optarg;
+                    const size_t colon = a.find(':');
+                    if (colon == std::string::npos) throw 1;
+                    ladderLo = (uint32_t)std::stoi(a.substr(0, colon));
+                    ladderHi = (uint32_t)std::stoi(a.substr(colon + 1));
+                    if (ladderLo < 2 || ladderHi > 64 || ladderLo > ladderHi) throw 1;
+                    break;
+                }
                 case 'S': seed = (uint32_t)std::stoi(optarg); break;
                 case 'D': device = std::stoi(optarg); break;
                 case 'F': simulate = fast = true; prob = std::stod(optarg);
@@ -214,6 +227,11 @@ int main(int argc, char** argv) {
                    chains > 1024 || nCol > 64)) {
         std::cout << "--chains R batches --mcmcgpu alone: 1 <= R <= 1024, --nCol <= 64, no --repet, --gpus > 1, "
                      "--tailcutRepair or other colorer" << std::endl;
+        return 255;
+    }
+    if (ladderLo && (!chains || nCol || chains % (ladderHi - ladderLo + 1))) {
+        std::cout << "--nColLadder LO:HI (2 <= LO <= HI <= 64) needs --chains R with R a multiple of HI - LO + 1, and no --nCol"
+                  << std::endl;
         return 255;
     }
     if (simulate && n == 0) { std::cout << "Simualtion enabled: specify the number of nodes (-n)." << std::endl; return 255; }
@@ -299,11 +317,17 @@ int main(int argc, char** argv) {
         params.maxRip = 250;
         params.tabooIteration = tabooIteration;
         params.tailcut = tailcut;
-        if (params.nCol > 64) {
+        if (!ladderLo && params.nCol > 64) {
             std::cout << "--chains needs nCol <= 64 (default nCol = " << params.nCol << ": give --nCol)" << std::endl;
             return 255;
         }
-        ColoringMCMCChains<float, float> batch(g, GPURandGen.randStates, params, chains);
+        std::vector<mcmc_chain_spec> specs;
+        for (uint32_t r = 0, K = ladderHi - ladderLo + 1; ladderLo && r < chains; r++)
+            specs.push_back(mcmc_chain_spec{ladderLo + r % K, seed + r / K, params.epsilon, 0u});
+        std::unique_ptr<ColoringMCMCChains<float, float>> bp(
+            ladderLo ? new ColoringMCMCChains<float, float>(g, params, specs)
+                     : new ColoringMCMCChains<float, float>(g, GPURandGen.randStates, params, chains));
+        ColoringMCMCChains<float, float>& batch = *bp;
         batch.run();
         uint64_t sweeps = 0;
         for (uint32_t r = 0; r < chains; r++) {
@@ -313,6 +337,14 @@ int main(int argc, char** argv) {
         std::cout << "MCMC GPU chains elapsed time: " << batch.getStats(0).loopMs / 1000.0 << " (" << chains
                   << " chains, " << sweeps << " chain-sweeps, rows from the "
                   << (batch.info()[0] ? "tiled layout" : "CSR") << ")" << std::endl;
+        if (ladderLo) {
+            const int best = batch.summary(std::cout);
+            if (best < 0)
+                std::cout << "best: none converged" << std::endl;
+            else
+                std::cout << "best: chain " << best << " nCol " << batch.spec(best).nCol << " seed " << batch.spec(best).seed
+                          << std::endl;
+        }
         repetitions = 0;
     }
     for (uint32_t i = 0; i < repetitions; i++) {
