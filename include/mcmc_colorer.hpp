@@ -368,6 +368,15 @@ public:
     ColoringMCMCChains(Graph<nodeW, edgeW>* inGraph_d, ColoringMCMCParams params, std::vector<mcmc_chain_spec> ladder)
         : graph(inGraph_d), seed(ladder.empty() ? 0u : ladder[0].seed), param(params), R((uint32_t)ladder.size()),
           specs(std::move(ladder)) {}
+    // The wide batch (mcmc_chains_create_wide): per-chain nCol up to 256. An empty ladder with chains > 0
+    // is the uniform wide batch (params.nCol, params.epsilon, seeds seed + r).
+    struct Wide {};
+    ColoringMCMCChains(Wide, Graph<nodeW, edgeW>* inGraph_d, GPURandHandle* randStates, ColoringMCMCParams params,
+                       uint32_t chains)
+        : graph(inGraph_d), seed(randStates->seed), param(params), R(chains), wide(true) {}
+    ColoringMCMCChains(Wide, Graph<nodeW, edgeW>* inGraph_d, ColoringMCMCParams params, std::vector<mcmc_chain_spec> ladder)
+        : graph(inGraph_d), seed(ladder.empty() ? 0u : ladder[0].seed), param(params), R((uint32_t)ladder.size()),
+          specs(std::move(ladder)), wide(true) {}
     ColoringMCMCChains(const ColoringMCMCChains&) = delete;
     ColoringMCMCChains& operator=(const ColoringMCMCChains&) = delete;
     ~ColoringMCMCChains() { mcmc_chains_destroy(ctx); }
@@ -385,7 +394,9 @@ public:
         p.tabooIteration = param.tabooIteration;
         p.tailcut = param.tailcut;
         p.seed = seed;
-        if (specs.empty())
+        if (wide)
+            MCMC_CHECK(mcmc_chains_create_wide(graph->handle(), &p, specs.empty() ? nullptr : specs.data(), R, &ctx));
+        else if (specs.empty())
             MCMC_CHECK(mcmc_chains_create(graph->handle(), &p, R, &ctx));   // a generated graph: its tiled layout, no CSR
         else
             MCMC_CHECK(mcmc_chains_create_ladder(graph->handle(), &p, specs.data(), R, &ctx));
@@ -401,7 +412,7 @@ public:
 
     uint32_t chains() const { return R; }
     // mcmc_chains_get_info: {adjacency source (0 CSR, 1 tiled layout), device bytes of the batch,
-    // vertices per wave, chain groups, sweep grid x, 0, 0, 0}; after run().
+    // vertices per wave, chain groups, sweep grid x, 1 for a ladder, mask words of the sweep, 0}; after run().
     std::vector<uint64_t> info() const {
         std::vector<uint64_t> w(8);
         MCMC_CHECK(mcmc_chains_get_info(ctx, w.data()));
@@ -412,10 +423,11 @@ public:
     mcmc_chain_spec spec(uint32_t r) const {
         return specs.empty() ? mcmc_chain_spec{param.nCol, seed + r, param.epsilon, 0u} : specs.at(r);
     }
-    // [chains][64] class sizes of every chain's colouring, counted on the device
-    std::vector<uint32_t> histograms() const {
-        std::vector<uint32_t> h((size_t)R * 64);
-        MCMC_CHECK(mcmc_chains_get_histograms(ctx, h.data()));
+    // [chains][cols] class sizes of every chain's colouring, counted on the device; cols >= the largest
+    // nCol (64 serves every narrow batch, 256 every batch)
+    std::vector<uint32_t> histograms(uint32_t cols = 64) const {
+        std::vector<uint32_t> h((size_t)R * cols);
+        MCMC_CHECK(mcmc_chains_get_histograms_n(ctx, h.data(), cols));
         return h;
     }
     // One line per chain (nCol, epsilon, seed, iter, maxIterReached, finalViol, used colours, min / max
@@ -423,7 +435,8 @@ public:
     // the converged ones the smallest nCol, then the smallest deviation, then the lowest index; -1 if
     // none converged. Host code over the device histograms.
     int summary(std::ostream& out) const {
-        const std::vector<uint32_t> h = histograms();
+        const uint32_t cols = wide ? 256u : 64u;
+        const std::vector<uint32_t> h = histograms(cols);
         int best = -1;
         double bestStd = 0;
         for (uint32_t r = 0; r < R; r++) {
@@ -432,14 +445,14 @@ public:
             uint32_t used = 0, mn = ~0u, mx = 0;
             double mean = 0, var = 0;
             for (uint32_t k = 0; k < sp.nCol; k++) {
-                const uint32_t x = h[(size_t)r * 64 + k];
+                const uint32_t x = h[(size_t)r * cols + k];
                 used += x ? 1 : 0;
                 mn = std::min(mn, x);
                 mx = std::max(mx, x);
                 mean += x;
             }
             mean /= sp.nCol;
-            for (uint32_t k = 0; k < sp.nCol; k++) var += (h[(size_t)r * 64 + k] - mean) * (h[(size_t)r * 64 + k] - mean);
+            for (uint32_t k = 0; k < sp.nCol; k++) var += (h[(size_t)r * cols + k] - mean) * (h[(size_t)r * cols + k] - mean);
             const double sd = std::sqrt(var / sp.nCol);
             out << "chain " << r << ": nCol " << sp.nCol << " epsilon " << sp.epsilon << " seed " << sp.seed << " iter "
                 << st.iter << " maxIterReached " << st.maxIterReached << " finalViol " << st.finalViol << " used " << used
@@ -515,6 +528,7 @@ private:
     ColoringMCMCParams param;
     uint32_t R;
     std::vector<mcmc_chain_spec> specs;   // a ladder's; empty: uniform
+    bool wide{false};                     // mcmc_chains_create_wide
     mcmc_chains* ctx{nullptr};
     std::vector<mcmc_run_stats> stats;
 };

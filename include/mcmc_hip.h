@@ -260,7 +260,8 @@ void mcmc_destroy(mcmc_ctx* c);
  * ColoringMCMC::run(i), where repetition i + 1 continues the one process stream where repetition i
  * stopped: chain r equals repetition r only when both start at the same window (always, while no
  * overflow occurs -- ~1e-7 per draw at the default epsilon).
- * Supported: 2 <= nCol <= 64 (one 64-bit occupancy mask per lane), 1 <= R <= 1024, a graph with a
+ * Supported: 2 <= nCol <= 64 (one 64-bit occupancy mask per lane; up to 256 through
+ * mcmc_chains_create_wide), 1 <= R <= 1024, a graph with a
  * whole device CSR (mcmc_graph_upload, _simulate, _rmat) or, when it has none, the full-range tiled
  * layout of mcmc_graph_er_fast, which the sweep reads as it is (block-local 16-bit ids; no CSR is
  * built, so the batch also runs where a CSR would not fit). A row-range graph
@@ -282,9 +283,20 @@ int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mc
 typedef struct { uint32_t nCol, seed; float epsilon; uint32_t reserved; } mcmc_chain_spec;
 int mcmc_chains_create_ladder(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_spec* specs, uint32_t R,
                               mcmc_chains** out);
+/* The wide batch: per-chain 2 <= nCol <= 256, the range of the byte-coloured single run. The two
+ * calls above keep a lane's occupancy in one 64-bit register pair; this one runs the wide sweep
+ * (csrc/chains_wide.h), whose per-lane occupancy is 4 (every nCol <= 128) or 8 words of a wave-private
+ * LDS table -- always, also when every nCol <= 64. specs == NULL: a uniform batch (p->nCol,
+ * p->epsilon, seeds p->seed + r); otherwise a ladder as mcmc_chains_create_ladder. 2 <= nCol <= 256
+ * and reserved == 0, else MCMC_E_ARG naming the chain; graph rules, memory rules and R limits are
+ * those of mcmc_chains_create, and every other mcmc_chains_* call works on the result. Chain r is,
+ * bit for bit, the single run with its own (nCol, epsilon, seed). */
+int mcmc_chains_create_wide(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_spec* specs /* may be NULL */,
+                            uint32_t R, mcmc_chains** out);
 /* out[0] adjacency source of the sweep (0 CSR, 1 tiled layout), [1] device bytes of the batch's own
  * allocation, [2] vertices per wave, [3] chain groups, [4] sweep grid x, [5] 1 for a ladder
- * (mcmc_chains_create_ladder), else 0, [6..7] 0. */
+ * (mcmc_chains_create_ladder, mcmc_chains_create_wide), else 0, [6] mask words of the sweep: 0 for
+ * the narrow kernels, 4 or 8 for the wide one, [7] 0. */
 int mcmc_chains_get_info(mcmc_chains* c, uint64_t out[8]);
 /* windows[R][31]; default: every chain at srand(1) with no draws (mcmc_set_glibc_window's default).
  * mcmc_chains_get_glibc_windows returns them advanced by each chain's glibcDraws. */
@@ -303,6 +315,10 @@ int mcmc_chains_get_coloring(mcmc_chains* c, uint32_t r, uint32_t* out /* n */);
  * R x 64 words copied back; computed on demand and kept until the next mcmc_chains_run. Both kinds
  * of batch. */
 int mcmc_chains_get_histograms(mcmc_chains* c, uint32_t* out /* [R][64] */);
+/* The same with rows of `cols` columns, cols >= the batch's largest nCol (else MCMC_E_ARG); any
+ * batch. A batch whose largest nCol is above 64 counts 256 colours per chain on the device, and
+ * mcmc_chains_get_histograms on it is MCMC_E_ARG. */
+int mcmc_chains_get_histograms_n(mcmc_chains* c, uint32_t* out /* [R][cols] */, uint32_t cols);
 int mcmc_chains_get_trajectory(mcmc_chains* c, uint32_t r, uint64_t* out, uint64_t cap, uint64_t* len);
 void mcmc_chains_destroy(mcmc_chains* c);
 

@@ -66,7 +66,9 @@ SIGNATURES: dict[str, tuple] = {
     "mcmc_destroy": (None, [c_void_p]),
     "mcmc_chains_create": (c_int, [c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
     "mcmc_chains_create_ladder": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
+    "mcmc_chains_create_wide": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
     "mcmc_chains_get_histograms": (c_int, [c_void_p, _u32p]),
+    "mcmc_chains_get_histograms_n": (c_int, [c_void_p, _u32p, c_uint32]),
     "mcmc_chains_get_info": (c_int, [c_void_p, _u64p]),
     "mcmc_chains_set_glibc_windows": (c_int, [c_void_p, _u32p]),
     "mcmc_chains_get_glibc_windows": (c_int, [c_void_p, _u32p]),

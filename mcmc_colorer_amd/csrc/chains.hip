@@ -64,6 +64,12 @@
 //   runs to the wave's largest live nCol (one wave reduction per block), a lane adding and testing
 //   only while k < nCol_l, in the same fp32 order as the single run. The commit draws
 //   rand() % (nCol_r - 1).
+// Wide (mcmc_chains_create_wide, chains_wide.h): per-chain nCol up to 256. chains_sweep_wide_kernel<TILED, MW>
+//   keeps the layout, the grid, the drain's wave-load, the row sources and everything from the update's
+//   taboo on; a chain's occupancy is MW = 4 or 8 words of a wave-private LDS table, set by ds_or_b32 with
+//   64 distinct columns per instruction, and read back by the chain's lane. The sweeps above are
+//   untouched: they read the byte table a.ncol, the wide sweep and the commit the 16-bit a.ncolw.
+//   Batches above 64 colours count their class sizes with chains_hist_wide_kernel (rows of 256).
 // Histograms (chains_hist_kernel): hist[r][k] = vertices of colour k in chain r's final colouring,
 //   read from the buffer each chain stopped in (selected per byte of the drain's dword), counted in
 //   an LDS table [64 chains][64 colours], one global atomic per nonzero cell and workgroup.
@@ -118,9 +124,10 @@ struct ChainArgs {
     uint32_t* ndone;        // chains that stopped
     // per chain (a ladder's differ; a uniform batch holds nCol, eps in every entry): the ladder
     // instantiations of the sweep, the commit's rand() % (nCol_r - 1)
-    const uint8_t* ncol;    // [G * 64], 0 past R
+    const uint8_t* ncol;    // [G * 64], 0 past R (the narrow ladder sweeps; a wide batch's entries are not read)
     const float* epsr;      // [G * 64]
-    uint32_t* hist;         // [G * 64][64] class sizes of the final colourings (chains_hist_kernel)
+    uint32_t* hist;         // [G * 64][64 or 256] class sizes of the final colourings (chains_hist_kernel / _wide_)
+    const uint16_t* ncolw;  // [G * 64], 0 past R: nCol up to 256 (the wide sweeps, the commit)
 };
 
 __device__ __forceinline__ uint64_t shfl64(uint64_t x, int src) {
@@ -450,7 +457,7 @@ __global__ __launch_bounds__(64) void chains_commit_kernel(ChainArgs a, uint32_t
         for (int o = 32; o > 0; o >>= 1) best = min(best, (uint32_t)__shfl_xor((int)best, o, 64));
         if (best == 0xFFFFFFFFu) break;
         if (lane == 0u) {
-            const uint32_t nc = glibc_next(ring, head) % ((uint32_t)a.ncol[r] - 1u);   // :518, the chain's own nCol
+            const uint32_t nc = glibc_next(ring, head) % ((uint32_t)a.ncolw[r] - 1u);   // :518, the chain's own nCol
             const size_t at = (size_t)best * kLanes + bit;
             Cn[at] = (uint8_t)nc;
             if (a.taboo) a.taboo[gofs + at] = (nc == Cc[at]) ? a.taboo_it : 0u;   // :526
@@ -559,6 +566,8 @@ __global__ __launch_bounds__(64 * kHistWaves) void chains_hist_kernel(ChainArgs 
     }
 }
 
+#include "chains_wide.h"
+
 }  // namespace
 }  // namespace mcmc
 
@@ -570,7 +579,9 @@ struct mcmc_chains {
     ChainArgs a{};
     bool tiled = false;           // the sweep reads the graph's tiled layout (no CSR), else the CSR
     bool ladder = false;          // mcmc_chains_create_ladder: the per-chain instantiations of the sweep
-    std::vector<uint32_t> hist;   // get_histograms: [R][64], valid until the next run
+    uint32_t mw = 0;              // mcmc_chains_create_wide: mask words of the wide sweep (4 or 8), else 0
+    uint32_t maxncol = 0;         // the batch's largest nCol; above 64 the histogram rows are 256 wide
+    std::vector<uint32_t> hist;   // get_histograms: [R][hist_cols()], valid until the next run
     bool hist_valid = false;
     size_t bytes = 0;             // of `mem`
     void* mem = nullptr;          // one device allocation behind every pointer of `a`
@@ -582,6 +593,7 @@ struct mcmc_chains {
     std::vector<ChainState> st;   // as of the last run
     std::vector<uint8_t> cache;   // get_coloring: one group's buffer
     int cache_g = -1, cache_buf = -1;
+    uint32_t hist_cols() const { return maxncol > 64u ? 256u : 64u; }
 };
 
 namespace {
@@ -621,10 +633,11 @@ int chains_upload_windows(mcmc_chains* c, const uint32_t* w /* [R][31], nullptr:
 namespace {
 
 // The batch of mcmc_chains_create (specs: nCol, epsilon of `p` and seed + r for every chain; the
-// uniform sweep) and of mcmc_chains_create_ladder (the caller's specs; the ladder sweep). The
+// uniform sweep), of mcmc_chains_create_ladder (the caller's specs; the ladder sweep) and of
+// mcmc_chains_create_wide (wide: the wide sweep, its mask words from the largest nCol). The
 // arguments other than the graph are checked by the callers.
 int chains_create(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_spec* specs, uint32_t R, bool ladder,
-                  mcmc_chains** out) {
+                  bool wide, mcmc_chains** out) {
     const GraphDev& gd = g->g;
     if (gd.n == 0) return fail(MCMC_E_ARG, "chains: empty graph");
     if (gd.partial_rows)
@@ -644,9 +657,11 @@ int chains_create(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_sp
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t b_col = up((size_t)n * kLanes * G), b_tab = p->tabooIteration ? up(4 * (size_t)n * kLanes * G) : 0;
     const size_t b_ev = up(sizeof(uint4) * (size_t)n * G), b_traj = up(4 * (size_t)R * traj_cap);
-    const size_t b_hist = up(4 * 64 * (size_t)RP);
+    uint32_t maxncol = 0;
+    for (uint32_t r = 0; r < R; r++) maxncol = std::max(maxncol, specs[r].nCol);
+    const size_t b_hist = up(4 * (maxncol > 64u ? 256 : 64) * (size_t)RP);
     const size_t b_small = up(4 * RP) * 2 + up(8 * RP) + up(4 * 1024) + up(8 * G) + up(sizeof(ChainState) * RP) +
-                           up(4 * 31 * (size_t)RP) + 256 + up(RP) + up(4 * RP) + up(sizeof(uint4) * RP) + b_hist;
+                           up(4 * 31 * (size_t)RP) + 256 + up(RP) + up(4 * RP) + up(sizeof(uint4) * RP) + b_hist + up(2 * RP);
     const size_t need = 2 * b_col + b_tab + b_ev + b_traj + b_small;
     size_t fr = 0, tot = 0;
     MCMC_HIP_TRY(hipMemGetInfo(&fr, &tot));
@@ -691,6 +706,8 @@ int chains_create(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_sp
     a.ncol = d_ncol;
     a.epsr = d_eps;
     a.hist = reinterpret_cast<uint32_t*>(take(b_hist));
+    uint16_t* d_ncolw = reinterpret_cast<uint16_t*>(take(2 * RP));
+    a.ncolw = d_ncolw;
     a.row_off = gd.row_off;
     a.col_idx = gd.col_idx;
     a.m = gd.m;
@@ -704,6 +721,8 @@ int chains_create(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_sp
     }
     c->tiled = L != nullptr;
     c->ladder = ladder;
+    c->mw = wide ? (maxncol > 128u ? 8u : 4u) : 0u;
+    c->maxncol = maxncol;
     c->bytes = need;
     a.n = n;
     a.R = R;
@@ -726,15 +745,18 @@ int chains_create(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_sp
     e = hipMemcpy(powtab, tab.data(), 4096, hipMemcpyHostToDevice);
     // per-chain tables: nCol, epsilon, and the init kernel's {seed, UniformIntConst}
     std::vector<uint8_t> h_ncol(RP, 0);
+    std::vector<uint16_t> h_ncolw(RP, 0);
     std::vector<float> h_eps(RP, 0.0f);
     std::vector<uint4> h_itab(RP, make_uint4(1u, 1u, 1u, 0u));
     for (uint32_t r = 0; r < R; r++) {
         const UniformIntConst k = uniform_int_const(specs[r].nCol);
         h_ncol[r] = (uint8_t)specs[r].nCol;
+        h_ncolw[r] = (uint16_t)specs[r].nCol;
         h_eps[r] = specs[r].epsilon;
         h_itab[r] = make_uint4(specs[r].seed, k.scaling, k.past, 0u);
     }
     if (e == hipSuccess) e = hipMemcpy(d_ncol, h_ncol.data(), RP, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_ncolw, h_ncolw.data(), 2 * (size_t)RP, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_eps, h_eps.data(), 4 * (size_t)RP, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_itab, h_itab.data(), sizeof(uint4) * (size_t)RP, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
@@ -766,7 +788,7 @@ int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mc
     if (R < 1 || R > kMaxChains) return fail(MCMC_E_ARG, "chains: 1 <= R <= 1024, got " + std::to_string(R));
     std::vector<mcmc_chain_spec> specs(R);
     for (uint32_t r = 0; r < R; r++) specs[r] = mcmc_chain_spec{p->nCol, p->seed + r, p->epsilon, 0u};
-    return chains_create(g, p, specs.data(), R, false, out);
+    return chains_create(g, p, specs.data(), R, false, false, out);
 }
 
 int mcmc_chains_create_ladder(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_spec* specs, uint32_t R,
@@ -781,12 +803,29 @@ int mcmc_chains_create_ladder(const mcmc_graph* g, const mcmc_params* p, const m
         if (specs[r].reserved != 0)
             return fail(MCMC_E_ARG, "chains: chain " + std::to_string(r) + ": reserved must be 0");
     }
-    return chains_create(g, p, specs, R, true, out);
+    return chains_create(g, p, specs, R, true, false, out);
+}
+
+int mcmc_chains_create_wide(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_spec* specs, uint32_t R,
+                            mcmc_chains** out) {
+    if (!g || !p || !out) return fail(MCMC_E_ARG, "NULL argument");
+    *out = nullptr;
+    if (R < 1 || R > kMaxChains) return fail(MCMC_E_ARG, "chains: 1 <= R <= 1024, got " + std::to_string(R));
+    std::vector<mcmc_chain_spec> sp(R);
+    for (uint32_t r = 0; r < R; r++) {
+        sp[r] = specs ? specs[r] : mcmc_chain_spec{p->nCol, p->seed + r, p->epsilon, 0u};
+        if (sp[r].nCol < 2 || sp[r].nCol > 256)
+            return fail(MCMC_E_ARG, "chains: chain " + std::to_string(r) + ": 2 <= nCol <= 256 (the wide sweep's occupancy "
+                                    "table), got " + std::to_string(sp[r].nCol));
+        if (sp[r].reserved != 0)
+            return fail(MCMC_E_ARG, "chains: chain " + std::to_string(r) + ": reserved must be 0");
+    }
+    return chains_create(g, p, sp.data(), R, true, true, out);
 }
 
 int mcmc_chains_get_info(mcmc_chains* c, uint64_t out[8]) {
     if (!c || !out) return fail(MCMC_E_ARG, "NULL argument");
-    const uint64_t w[8] = {c->tiled ? 1u : 0u, c->bytes, c->a.vb, c->a.G, chains_grid_x(c->a), c->ladder ? 1u : 0u, 0u, 0u};
+    const uint64_t w[8] = {c->tiled ? 1u : 0u, c->bytes, c->a.vb, c->a.G, chains_grid_x(c->a), c->ladder ? 1u : 0u, c->mw, 0u};
     std::memcpy(out, w, sizeof(w));
     return MCMC_OK;
 }
@@ -834,7 +873,15 @@ int mcmc_chains_run(mcmc_chains* c, uint32_t max_sweeps, mcmc_run_stats* stats) 
         const uint32_t b = std::min(kPollSweeps, total - k);
         for (uint32_t j = 0; j < b; j++, c->t++) {
             const uint32_t tn = (uint32_t)(((uint64_t)c->t * a.n) % kMinstdN);
-            if (c->tiled && c->ladder)
+            if (c->mw == 8u && c->tiled)
+                chains_sweep_wide_kernel<true, 8><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+            else if (c->mw == 8u)
+                chains_sweep_wide_kernel<false, 8><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+            else if (c->mw == 4u && c->tiled)
+                chains_sweep_wide_kernel<true, 4><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+            else if (c->mw == 4u)
+                chains_sweep_wide_kernel<false, 4><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+            else if (c->tiled && c->ladder)
                 chains_sweep_kernel<true, true><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
             else if (c->tiled)
                 chains_sweep_kernel<true, false><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
@@ -893,25 +940,45 @@ int mcmc_chains_get_coloring(mcmc_chains* c, uint32_t r, uint32_t* out) {
     return MCMC_OK;
 }
 
-int mcmc_chains_get_histograms(mcmc_chains* c, uint32_t* out) {
+int mcmc_chains_get_histograms_n(mcmc_chains* c, uint32_t* out, uint32_t cols) {
     if (!c || !out) return fail(MCMC_E_ARG, "NULL argument");
+    if (cols < c->maxncol)
+        return fail(MCMC_E_ARG, "chains: histogram rows of " + std::to_string(cols) + " colours, the batch's largest nCol is " +
+                                    std::to_string(c->maxncol));
     MCMC_HIP_TRY(hipSetDevice(c->g->g.device));
     const ChainArgs& a = c->a;
+    const uint32_t hc = c->hist_cols();
     if (!c->hist_valid) {   // computed on demand, kept until the next run
         // vertices per workgroup: 1024, more once that makes over ~1024 workgroups per group (each
         // flushes up to 64 x nCol cells); a multiple of the 32 a wave takes per turn
-        const uint32_t hv = (std::max(1024u, (uint32_t)(((uint64_t)a.n + 1023u) / 1024u)) + 31u) & ~31u;
+        uint32_t hv = (std::max(1024u, (uint32_t)(((uint64_t)a.n + 1023u) / 1024u)) + 31u) & ~31u;
+        if (hc == 256u) hv = std::min(hv, kHistWideMaxV);
         const dim3 grid((a.n + hv - 1u) / hv, a.G);
-        MCMC_HIP_TRY(hipMemsetAsync(a.hist, 0, 4 * 64 * (size_t)a.G * kLanes, c->stream));
-        chains_hist_kernel<<<grid, 64 * kHistWaves, 0, c->stream>>>(a, c->t, hv);
+        MCMC_HIP_TRY(hipMemsetAsync(a.hist, 0, 4 * (size_t)hc * a.G * kLanes, c->stream));
+        if (hc == 256u)
+            chains_hist_wide_kernel<<<grid, 64 * kHistWideWaves, 0, c->stream>>>(a, c->t, hv);
+        else
+            chains_hist_kernel<<<grid, 64 * kHistWaves, 0, c->stream>>>(a, c->t, hv);
         MCMC_HIP_TRY(hipGetLastError());
-        c->hist.resize((size_t)a.R * 64u);
+        c->hist.resize((size_t)a.R * hc);
         MCMC_HIP_TRY(hipMemcpyAsync(c->hist.data(), a.hist, 4 * c->hist.size(), hipMemcpyDeviceToHost, c->stream));
         MCMC_HIP_TRY(hipStreamSynchronize(c->stream));
         c->hist_valid = true;
     }
-    std::memcpy(out, c->hist.data(), 4 * c->hist.size());
+    const uint32_t k = std::min(cols, hc);   // columns past the kernel's row are colours no chain has
+    for (uint32_t r = 0; r < a.R; r++) {
+        std::memcpy(out + (size_t)r * cols, c->hist.data() + (size_t)r * hc, 4 * (size_t)k);
+        std::memset(out + (size_t)r * cols + k, 0, 4 * (size_t)(cols - k));
+    }
     return MCMC_OK;
+}
+
+int mcmc_chains_get_histograms(mcmc_chains* c, uint32_t* out) {
+    if (!c || !out) return fail(MCMC_E_ARG, "NULL argument");
+    if (c->maxncol > 64u)
+        return fail(MCMC_E_ARG, "chains: the batch's largest nCol is " + std::to_string(c->maxncol) +
+                                    ": its histogram rows do not fit 64 columns (mcmc_chains_get_histograms_n)");
+    return mcmc_chains_get_histograms_n(c, out, 64u);
 }
 
 int mcmc_chains_get_trajectory(mcmc_chains* c, uint32_t r, uint64_t* out, uint64_t cap, uint64_t* len) {
