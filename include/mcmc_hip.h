@@ -268,7 +268,8 @@ void mcmc_destroy(mcmc_ctx* c);
  * (mcmc_graph_er_fast_rows / _part) and anything else is MCMC_E_ARG. Device memory: 2 n 64 ceil(R / 64) bytes of
  * colours, 4 times half of that again for the taboo counters when tabooIteration > 0, 16 n
  * ceil(R / 64) bytes of overflow records, the trajectories; MCMC_E_NOMEM with the byte counts when
- * it does not fit. The context borrows `g`. */
+ * it does not fit. The context borrows `g` for every call but mcmc_chains_destroy, which does not
+ * read it (a garbage collector may finalise the graph's wrapper before the batch's). */
 typedef struct mcmc_chains mcmc_chains;
 /* params.seed is chain 0's seed. Draws every chain's initial colouring (mcmc_init_coloring's). */
 int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mcmc_chains** out);

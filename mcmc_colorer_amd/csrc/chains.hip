@@ -575,6 +575,7 @@ using namespace mcmc;
 
 struct mcmc_chains {
     const mcmc_graph* g = nullptr;
+    int device = 0;               // g's device: mcmc_chains_destroy must not read g (it may be gone by then)
     mcmc_params p{};
     ChainArgs a{};
     bool tiled = false;           // the sweep reads the graph's tiled layout (no CSR), else the CSR
@@ -671,6 +672,7 @@ int chains_create(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_sp
                                       ", trajectories " + std::to_string(b_traj) + "), " + std::to_string(fr) + " free");
     mcmc_chains* c = new mcmc_chains();
     c->g = g;
+    c->device = gd.device;
     c->p = *p;
     hipError_t e = hipMalloc(&c->mem, need);
     if (e == hipSuccess) e = hipMemset(c->mem, 0, need);
@@ -1003,7 +1005,7 @@ int mcmc_chains_get_trajectory(mcmc_chains* c, uint32_t r, uint64_t* out, uint64
 
 void mcmc_chains_destroy(mcmc_chains* c) {
     if (!c) return;
-    (void)hipSetDevice(c->g->g.device);
+    (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->mem) (void)hipFree(c->mem);
     if (c->pinned) (void)hipHostFree(c->pinned);
