@@ -381,6 +381,10 @@ public:
     ColoringMCMCChains& operator=(const ColoringMCMCChains&) = delete;
     ~ColoringMCMCChains() { mcmc_chains_destroy(ctx); }
 
+    // The batched tail cut after the loop (mcmc_chains_enable_repair): at most maxPasses passes per
+    // chain; 0 (the default) disables it. Takes effect at the next run().
+    void setRepair(uint32_t maxPasses) { repair = maxPasses; }
+
     void run() {
         mcmc_chains_destroy(ctx);
         ctx = nullptr;
@@ -401,6 +405,7 @@ public:
         else
             MCMC_CHECK(mcmc_chains_create_ladder(graph->handle(), &p, specs.data(), R, &ctx));
         MCMC_CHECK(mcmc_chains_set_tailcut_repair(ctx, param.tailcutRepair));
+        if (repair) MCMC_CHECK(mcmc_chains_enable_repair(ctx, repair));
         std::vector<uint32_t> w((size_t)R * 31);
         for (uint32_t r = 0; r < R; r++) std::memcpy(&w[(size_t)r * 31], mcmc::glibc_global().w, 31 * sizeof(uint32_t));
         MCMC_CHECK(mcmc_chains_set_glibc_windows(ctx, w.data()));
@@ -412,7 +417,8 @@ public:
 
     uint32_t chains() const { return R; }
     // mcmc_chains_get_info: {adjacency source (0 CSR, 1 tiled layout), device bytes of the batch,
-    // vertices per wave, chain groups, sweep grid x, 1 for a ladder, mask words of the sweep, 0}; after run().
+    // vertices per wave, chain groups, sweep grid x, 1 for a ladder, mask words of the sweep, microseconds
+    // of the tail-cut repair}; after run().
     std::vector<uint64_t> info() const {
         std::vector<uint64_t> w(8);
         MCMC_CHECK(mcmc_chains_get_info(ctx, w.data()));
@@ -430,10 +436,11 @@ public:
         MCMC_CHECK(mcmc_chains_get_histograms_n(ctx, h.data(), cols));
         return h;
     }
-    // One line per chain (nCol, epsilon, seed, iter, maxIterReached, finalViol, used colours, min / max
-    // class size, deviation of the class sizes over nCol) and the index of the chain to keep: among
-    // the converged ones the smallest nCol, then the smallest deviation, then the lowest index; -1 if
-    // none converged. Host code over the device histograms.
+    // One line per chain (nCol, epsilon, seed, iter, maxIterReached, finalViol, with setRepair the
+    // tail-cut passes, used colours, min / max class size, deviation of the class sizes over nCol) and
+    // the index of the chain to keep: among the converged ones and those the repair left proper the
+    // smallest nCol, then the smallest deviation, then the lowest index; -1 if there is none. Host code
+    // over the device histograms.
     int summary(std::ostream& out) const {
         const uint32_t cols = wide ? 256u : 64u;
         const std::vector<uint32_t> h = histograms(cols);
@@ -455,9 +462,11 @@ public:
             for (uint32_t k = 0; k < sp.nCol; k++) var += (h[(size_t)r * cols + k] - mean) * (h[(size_t)r * cols + k] - mean);
             const double sd = std::sqrt(var / sp.nCol);
             out << "chain " << r << ": nCol " << sp.nCol << " epsilon " << sp.epsilon << " seed " << sp.seed << " iter "
-                << st.iter << " maxIterReached " << st.maxIterReached << " finalViol " << st.finalViol << " used " << used
+                << st.iter << " maxIterReached " << st.maxIterReached << " finalViol " << st.finalViol;
+            if (repair) out << " tailcutPasses " << st.tailcutPasses;
+            out << " used " << used
                 << " min " << mn << " max " << mx << " std " << sd << std::endl;
-            if (!st.maxIterReached &&
+            if ((!st.maxIterReached || (st.tailcutPasses > 0 && st.finalViol == 0)) &&
                 (best < 0 || sp.nCol < spec(best).nCol || (sp.nCol == spec(best).nCol && sd < bestStd))) {
                 best = (int)r;
                 bestStd = sd;
@@ -529,6 +538,7 @@ private:
     uint32_t R;
     std::vector<mcmc_chain_spec> specs;   // a ladder's; empty: uniform
     bool wide{false};                     // mcmc_chains_create_wide
+    uint32_t repair{0};                   // mcmc_chains_enable_repair's max_passes
     mcmc_chains* ctx{nullptr};
     std::vector<mcmc_run_stats> stats;
 };

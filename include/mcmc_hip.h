@@ -297,7 +297,8 @@ int mcmc_chains_create_wide(const mcmc_graph* g, const mcmc_params* p, const mcm
 /* out[0] adjacency source of the sweep (0 CSR, 1 tiled layout), [1] device bytes of the batch's own
  * allocation, [2] vertices per wave, [3] chain groups, [4] sweep grid x, [5] 1 for a ladder
  * (mcmc_chains_create_ladder, mcmc_chains_create_wide), else 0, [6] mask words of the sweep: 0 for
- * the narrow kernels, 4 or 8 for the wide one, [7] 0. */
+ * the narrow kernels, 4 or 8 for the wide one, [7] the tail-cut repair's time on the stream in
+ * microseconds (hipEvent; 0 until mcmc_chains_enable_repair's repair ran). */
 int mcmc_chains_get_info(mcmc_chains* c, uint64_t out[8]);
 /* windows[R][31]; default: every chain at srand(1) with no draws (mcmc_set_glibc_window's default).
  * mcmc_chains_get_glibc_windows returns them advanced by each chain's glibcDraws. */
@@ -306,6 +307,21 @@ int mcmc_chains_get_glibc_windows(mcmc_chains* c, uint32_t* windows /* [R][31] *
 /* The tail-cut repair of mcmc_set_tailcut_repair is not available to chains: max_passes > 0 is
  * MCMC_E_ARG (0 is accepted). */
 int mcmc_chains_set_tailcut_repair(mcmc_chains* c, uint32_t max_passes);
+/* The batched tail cut (csrc/chains_tailcut.h): after the mcmc_chains_run call in which the last chain
+ * stops, every chain that stopped with violators is repaired as mcmc_set_tailcut_repair repairs a
+ * single run -- chain r ends, bit for bit, as the oracle's run with tailcutRepair and its own (nCol,
+ * epsilon, seed): colorIdx sorted by ascending class size when params.tailcut, at most max_passes
+ * Gauss-Seidel passes over the chain's flagged vertices, the first of them over the flags of the
+ * colouring before the last accepted sweep. stats then hold the repaired Cviol in finalViol and the
+ * passes in tailcutPasses (a chain whose pass k >= 2 changed nothing is at a fixed point and reports
+ * max_passes without running them); the trajectory, iter and loopMs stay the loop's, and
+ * mcmc_chains_get_coloring / _histograms return the repaired colourings. A run cut short by max_sweeps
+ * repairs nothing. Call it before the first mcmc_chains_run: it allocates 28 n ceil(R / 64) bytes of
+ * flag words and lists and selects the sweeps that keep the flags; after a run has started it is
+ * MCMC_E_ARG. max_passes = 0 disables it. Two calls because mcmc_chains_set_tailcut_repair's refusal
+ * of max_passes > 0 is a documented behaviour that callers and tests rely on: the capability has an
+ * entry point of its own, as mcmc_chains_create_wide has. */
+int mcmc_chains_enable_repair(mcmc_chains* c, uint32_t max_passes);
 /* Every chain's run() loop; each stops at its own sweep. max_sweeps > 0: at most that many sweeps
  * (chains still running then report iter = sweeps, finalViol = ~0, as mcmc_run; a later call
  * continues). stats[R] (may be NULL): per chain, loopMs = the batch's device time (hipEvent). */

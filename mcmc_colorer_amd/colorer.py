@@ -363,14 +363,16 @@ class ColoringMCMCChains:
     whose position every chain starts at, or a list of ``chains`` of them; advanced in place by
     ``run()``), where ``ColoringMCMC.run(i + 1)`` continues the stream ``run(i)`` left. 2 <= nCol <= 64,
     1 <= chains <= 1024, a graph with a device CSR or a whole ``Graph.er_fast`` graph, whose tiled
-    16-bit layout the sweep reads as it is (no CSR is built); no tail-cut repair.
+    16-bit layout the sweep reads as it is (no CSR is built). ``repair=N`` (here and in ``ladder``)
+    runs the batched tail cut after the loop, mcmc_chains_enable_repair: at most N passes per chain,
+    chain r as the single run with ``tailcutRepair``; ``params.tailcutRepair`` itself stays refused.
     ``ColoringMCMCChains.ladder`` gives every chain its own nCol, epsilon and seed; ``histograms()``,
     ``summary()`` and ``best()`` compare the chains from class sizes counted on the device.
     ``wide=True`` (here and in ``ladder``) runs the wide sweep, mcmc_chains_create_wide: 2 <= nCol <=
     256 per chain, the occupancy masks in LDS; ``histograms()`` then has 256 columns."""
 
     def __init__(self, graph: Graph, params: ColoringMCMCParams, seed: int, chains: int, glibc=None, specs=None,
-                 wide: bool = False):
+                 wide: bool = False, repair: int = 0):
         if params.nCol == 0 and specs is None:
             params = ColoringMCMCParams(**{**params.__dict__, "nCol": default_ncol(graph, params)})
         self.graph, self.param, self.seed, self.chains = graph, params, seed, int(chains)
@@ -391,19 +393,23 @@ class ColoringMCMCChains:
             create = lib().mcmc_chains_create_wide if wide else lib().mcmc_chains_create_ladder
             check(create(graph.handle, ctypes.byref(self._cparams), arr, self.chains, ctypes.byref(self._h)))
         check(lib().mcmc_chains_set_tailcut_repair(self._h, int(params.tailcutRepair)))
+        if repair:
+            check(lib().mcmc_chains_enable_repair(self._h, int(repair)))
         if glibc is None:
             glibc = GlibcRand(1)
         self.glibc = [glibc] * self.chains if isinstance(glibc, GlibcRand) else list(glibc)
         self._stats: list[MCMCRunStats] = []
 
     @classmethod
-    def ladder(cls, graph: Graph, params: ColoringMCMCParams, specs, glibc=None, wide: bool = False) -> "ColoringMCMCChains":
+    def ladder(cls, graph: Graph, params: ColoringMCMCParams, specs, glibc=None, wide: bool = False,
+               repair: int = 0) -> "ColoringMCMCChains":
         """One batch whose chain r has its own ``specs[r] = (nCol, epsilon, seed)`` (2 <= nCol <= 64, or
         <= 256 with ``wide=True``): mcmc_chains_create_ladder / mcmc_chains_create_wide. ``params``
         supplies maxRip, tabooIteration and tailcut; its nCol and epsilon are ignored. Chain r equals the
         single run with its own three values, bit for bit."""
         specs = list(specs)
-        return cls(graph, params, specs[0][2] if specs else 0, len(specs), glibc=glibc, specs=specs, wide=wide)
+        return cls(graph, params, specs[0][2] if specs else 0, len(specs), glibc=glibc, specs=specs, wide=wide,
+                   repair=repair)
 
     def run(self, max_sweeps: int = 0) -> list[MCMCRunStats]:
         w = np.ascontiguousarray(np.stack([g.window for g in self.glibc]), dtype=np.uint32)
@@ -423,7 +429,7 @@ class ColoringMCMCChains:
     def info(self) -> list[int]:
         """mcmc_chains_get_info: [adjacency source (0 CSR, 1 tiled layout), device bytes of the batch,
         vertices per wave, chain groups, sweep grid x, 1 for a ladder, mask words of the sweep (0 narrow,
-        4 or 8 wide), 0]."""
+        4 or 8 wide), microseconds of the tail-cut repair]."""
         out = np.zeros(8, dtype=np.uint64)
         check(lib().mcmc_chains_get_info(self._h, u64ptr(out)))
         return [int(x) for x in out]
@@ -439,7 +445,7 @@ class ColoringMCMCChains:
         return out
 
     def summary(self) -> list[dict]:
-        """Per chain, after run(): nCol, epsilon, seed, iter, maxIterReached, finalViol, used colours,
+        """Per chain, after run(): nCol, epsilon, seed, iter, maxIterReached, finalViol, tailcutPasses, used colours,
         min / max class size and the standard deviation of the class sizes over nCol."""
         hist = self.histograms()
         res = []
@@ -447,13 +453,16 @@ class ColoringMCMCChains:
             h = hist[r, :k].astype(np.float64)
             res.append({"chain": r, "nCol": k, "epsilon": e, "seed": s, "iter": st.iter,
                         "maxIterReached": int(st.maxIterReached), "finalViol": st.finalViol,
+                        "tailcutPasses": st.tailcutPasses,
                         "used": int((h > 0).sum()), "min": int(h.min()), "max": int(h.max()), "std": float(h.std())})
         return res
 
     def best(self):
-        """The summary row of the chain to keep: among those that converged (maxIterReached == 0) the
-        smallest nCol, then the smallest deviation, then the lowest index; None if none converged."""
-        ok = [d for d in self.summary() if d["maxIterReached"] == 0]
+        """The summary row of the chain to keep: among those that converged (maxIterReached == 0) or
+        that the tail-cut repair left proper (tailcutPasses > 0, finalViol == 0) the smallest nCol, then
+        the smallest deviation, then the lowest index; None if there is none."""
+        ok = [d for d in self.summary()
+              if d["maxIterReached"] == 0 or (d["tailcutPasses"] > 0 and d["finalViol"] == 0)]
         return min(ok, key=lambda d: (d["nCol"], d["std"], d["chain"])) if ok else None
 
     def colorings(self) -> np.ndarray:

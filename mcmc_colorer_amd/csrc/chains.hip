@@ -70,6 +70,9 @@
 //   64 distinct columns per instruction, and read back by the chain's lane. The sweeps above are
 //   untouched: they read the byte table a.ncol, the wide sweep and the commit the 16-bit a.ncolw.
 //   Batches above 64 colours count their class sizes with chains_hist_wide_kernel (rows of 256).
+// Tail cut (mcmc_chains_enable_repair, chains_tailcut.h): after the loop every chain that stopped with
+//   violators is repaired as the single run's corrected tail cut repairs it, 64 chains per row read; the
+//   sweeps' FLAGS instantiations keep the violator ballots its first pass needs.
 // Histograms (chains_hist_kernel): hist[r][k] = vertices of colour k in chain r's final colouring,
 //   read from the buffer each chain stopped in (selected per byte of the drain's dword), counted in
 //   an LDS table [64 chains][64 colours], one global atomic per nonzero cell and workgroup.
@@ -128,6 +131,7 @@ struct ChainArgs {
     const float* epsr;      // [G * 64]
     uint32_t* hist;         // [G * 64][64 or 256] class sizes of the final colourings (chains_hist_kernel / _wide_)
     const uint16_t* ncolw;  // [G * 64], 0 past R: nCol up to 256 (the wide sweeps, the commit)
+    uint64_t* vfl;          // [2][G][n] violator ballots of sweep t in vfl[t & 1] (the FLAGS sweeps; chains_tailcut.h)
 };
 
 __device__ __forceinline__ uint64_t shfl64(uint64_t x, int src) {
@@ -213,7 +217,10 @@ __device__ __forceinline__ uint32_t tiled_chunk(const uint16_t* __restrict__ ids
 // has its own nCol_r, eps_r (a.ncol, a.epsr). What differs: the masks' start values and the exit test
 // (MCMC_DRAIN_CHUNK), and in the update full, hi, fr, ps and the walk's end are per lane; the walk
 // runs to the wave's largest live nCol, a lane adding and testing only while k < nCol_l.
-template <bool TILED, bool LADDER>
+// FLAGS = true (mcmc_chains_enable_repair): lane 0 also keeps the ballot of `viol` per (group, v) in
+// a.vfl[t & 1], merged under the live mask so that a stopped chain keeps its bits. One wave owns a
+// (group, v): no atomic.
+template <bool TILED, bool LADDER, bool FLAGS>
 __global__ __launch_bounds__(64 * kSweepWaves) void chains_sweep_kernel(ChainArgs a, uint32_t t, uint32_t tn) {
     if (*a.ndone >= a.R) return;   // every chain stopped (workgroup-uniform)
     __shared__ uint32_t s_viol[kLanes];
@@ -343,6 +350,11 @@ __global__ __launch_bounds__(64 * kSweepWaves) void chains_sweep_kernel(ChainArg
             const uint32_t c = Cb[(size_t)v * kLanes + lane];
             const bool viol = (mask >> c) & 1ull;
             nviol += (live && viol) ? 1u : 0u;
+            if constexpr (FLAGS) {
+                const uint64_t fb = __ballot(viol);
+                uint64_t* fw = a.vfl + ((size_t)(t & 1u) * a.G + g) * n + v;
+                if (lane == 0u) *fw = (*fw & ~livemask) | (fb & livemask);
+            }
             const uint32_t Zv = (uint32_t)__popcll(mask);
             uint32_t tb = tab ? tab[(size_t)v * kLanes + lane] : 0u;
             uint32_t newc = c;
@@ -567,6 +579,7 @@ __global__ __launch_bounds__(64 * kHistWaves) void chains_hist_kernel(ChainArgs 
 }
 
 #include "chains_wide.h"
+#include "chains_tailcut.h"
 
 }  // namespace
 }  // namespace mcmc
@@ -594,6 +607,16 @@ struct mcmc_chains {
     std::vector<ChainState> st;   // as of the last run
     std::vector<uint8_t> cache;   // get_coloring: one group's buffer
     int cache_g = -1, cache_buf = -1;
+    // tail-cut repair (mcmc_chains_enable_repair; chains_tailcut.h)
+    uint32_t repair_max = 0;      // passes at most; 0: off
+    bool repaired = false;        // the repair ran (once, after the run in which the last chain stopped)
+    void* rmem = nullptr;         // one device allocation behind a.vfl and every pointer of `ta`
+    size_t rbytes = 0;
+    TailArgs ta{};
+    uint32_t* rpin = nullptr;     // a pass's counts and changed bits, pinned: [G * 64] + 2 [G]
+    std::vector<uint32_t> rep_passes;   // per chain; empty until the repair ran
+    std::vector<uint64_t> rep_viol;
+    float repair_ms = 0.0f;
     uint32_t hist_cols() const { return maxncol > 64u ? 256u : 64u; }
 };
 
@@ -632,6 +655,151 @@ int chains_upload_windows(mcmc_chains* c, const uint32_t* w /* [R][31], nullptr:
 }  // namespace
 
 namespace {
+
+template <bool FLAGS>
+void chains_launch_sweep(mcmc_chains* c, dim3 grid, uint32_t tn) {
+    const ChainArgs& a = c->a;
+    if (c->mw == 8u && c->tiled)
+        chains_sweep_wide_kernel<true, 8, FLAGS><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+    else if (c->mw == 8u)
+        chains_sweep_wide_kernel<false, 8, FLAGS><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+    else if (c->mw == 4u && c->tiled)
+        chains_sweep_wide_kernel<true, 4, FLAGS><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+    else if (c->mw == 4u)
+        chains_sweep_wide_kernel<false, 4, FLAGS><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+    else if (c->tiled && c->ladder)
+        chains_sweep_kernel<true, true, FLAGS><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+    else if (c->tiled)
+        chains_sweep_kernel<true, false, FLAGS><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+    else if (c->ladder)
+        chains_sweep_kernel<false, true, FLAGS><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+    else
+        chains_sweep_kernel<false, false, FLAGS><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+}
+
+// c->hist: the class sizes of every chain's colouring, [R][hist_cols()]; computed on demand, kept
+// until the next run
+int chains_histograms(mcmc_chains* c) {
+    if (c->hist_valid) return MCMC_OK;
+    const ChainArgs& a = c->a;
+    const uint32_t hc = c->hist_cols();
+    // vertices per workgroup: 1024, more once that makes over ~1024 workgroups per group (each
+    // flushes up to 64 x nCol cells); a multiple of the 32 a wave takes per turn
+    uint32_t hv = (std::max(1024u, (uint32_t)(((uint64_t)a.n + 1023u) / 1024u)) + 31u) & ~31u;
+    if (hc == 256u) hv = std::min(hv, kHistWideMaxV);
+    const dim3 grid((a.n + hv - 1u) / hv, a.G);
+    MCMC_HIP_TRY(hipMemsetAsync(a.hist, 0, 4 * (size_t)hc * a.G * kLanes, c->stream));
+    if (hc == 256u)
+        chains_hist_wide_kernel<<<grid, 64 * kHistWideWaves, 0, c->stream>>>(a, c->t, hv);
+    else
+        chains_hist_kernel<<<grid, 64 * kHistWaves, 0, c->stream>>>(a, c->t, hv);
+    MCMC_HIP_TRY(hipGetLastError());
+    c->hist.resize((size_t)a.R * hc);
+    MCMC_HIP_TRY(hipMemcpyAsync(c->hist.data(), a.hist, 4 * c->hist.size(), hipMemcpyDeviceToHost, c->stream));
+    MCMC_HIP_TRY(hipStreamSynchronize(c->stream));
+    c->hist_valid = true;
+    return MCMC_OK;
+}
+
+// The corrected tail cut of every chain that stopped with violators (chains_tailcut.h), after the run
+// in which the last chain stopped. c->st is the state at loop exit.
+int chains_repair(mcmc_chains* c) {
+    const ChainArgs& a = c->a;
+    const TailArgs& ta = c->ta;
+    const uint32_t R = a.R, G = a.G, n = a.n;
+    c->rep_passes.assign(R, 0u);
+    c->rep_viol.resize(R);
+    TailMasks act{}, buf1{}, par1{};
+    bool any = false;
+    for (uint32_t r = 0; r < R; r++) {
+        const ChainState& h = c->st[r];
+        c->rep_viol[r] = h.finalViol;
+        if (h.buf & 1u) buf1.m[r >> 6] |= 1ull << (r & 63u);
+        if (h.iter >= 1u && ((h.iter - 1u) & 1u)) par1.m[r >> 6] |= 1ull << (r & 63u);   // flags of C_{iter-1}
+        if (h.finalViol > 0u) {
+            act.m[r >> 6] |= 1ull << (r & 63u);
+            any = true;
+        }
+    }
+    MCMC_HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    const dim3 ngrid((uint32_t)(((uint64_t)n * 16u + 255u) / 256u), G);
+    chains_tail_normalise_kernel<<<ngrid, 256, 0, c->stream>>>(a, ta, buf1, par1);
+    MCMC_HIP_TRY(hipGetLastError());
+    for (auto& h : c->st) h.buf = 0u;
+    MCMC_HIP_TRY(hipMemcpyAsync(a.st, c->st.data(), sizeof(ChainState) * R, hipMemcpyHostToDevice, c->stream));
+    MCMC_HIP_TRY(hipStreamSynchronize(c->stream));   // c->st may change under the caller from here on
+    if (any) {
+        // colorIdx: the identity (:131-132); with z > 0 sorted by ascending class size (:272-278), by
+        // std::sort with the reference's comparator, so ties resolve as the reference's do
+        std::vector<uint8_t> cidx((size_t)G * kLanes * 256u, 0);
+        if (a.z > 0u) {
+            int rc = chains_histograms(c);
+            if (rc) return rc;
+        }
+        const uint32_t hc = c->hist_cols();
+        std::vector<uint16_t> ncol(R);
+        MCMC_HIP_TRY(hipMemcpy(ncol.data(), a.ncolw, 2 * (size_t)R, hipMemcpyDeviceToHost));
+        for (uint32_t r = 0; r < R; r++) {
+            const uint32_t k = ncol[r];
+            std::vector<size_t> colorIdx(k);
+            for (uint32_t i = 0; i < k; i++) colorIdx[i] = i;
+            if (a.z > 0u && c->rep_viol[r] > 0u) {
+                std::vector<size_t> histBins(c->hist.begin() + (size_t)r * hc, c->hist.begin() + (size_t)r * hc + k);
+                std::sort(colorIdx.begin(), colorIdx.end(), [&](int i, int j) { return histBins[i] < histBins[j]; });
+            }
+            for (uint32_t i = 0; i < k; i++) cidx[(size_t)r * 256u + i] = (uint8_t)colorIdx[i];
+        }
+        MCMC_HIP_TRY(hipMemcpyAsync(ta.cidx, cidx.data(), cidx.size(), hipMemcpyHostToDevice, c->stream));
+        MCMC_HIP_TRY(hipStreamSynchronize(c->stream));   // cidx leaves scope
+    }
+    const dim3 cgrid(chains_grid_x(a), G);
+    const uint32_t RP = G * kLanes;
+    for (uint32_t pass = 1; any && pass <= c->repair_max; pass++) {
+        chains_tail_list_kernel<<<G, kTailListThreads, 0, c->stream>>>(a, ta, act);
+        if (c->tiled && c->maxncol > 128u)
+            chains_tail_repair_kernel<true, 8><<<G, 64 * kTailWaves, 0, c->stream>>>(a, ta, act);
+        else if (c->tiled)
+            chains_tail_repair_kernel<true, 4><<<G, 64 * kTailWaves, 0, c->stream>>>(a, ta, act);
+        else if (c->maxncol > 128u)
+            chains_tail_repair_kernel<false, 8><<<G, 64 * kTailWaves, 0, c->stream>>>(a, ta, act);
+        else
+            chains_tail_repair_kernel<false, 4><<<G, 64 * kTailWaves, 0, c->stream>>>(a, ta, act);
+        if (c->tiled)
+            chains_tail_count_kernel<true><<<cgrid, 64 * kSweepWaves, 0, c->stream>>>(a, ta, act);
+        else
+            chains_tail_count_kernel<false><<<cgrid, 64 * kSweepWaves, 0, c->stream>>>(a, ta, act);
+        MCMC_HIP_TRY(hipGetLastError());
+        // one small copy: the R counts and the groups' changed bits (contiguous on the device)
+        MCMC_HIP_TRY(hipMemcpyAsync(c->rpin, ta.cnt, 4 * (size_t)RP + 8 * (size_t)G, hipMemcpyDeviceToHost, c->stream));
+        MCMC_HIP_TRY(hipStreamSynchronize(c->stream));
+        uint64_t chg[kMaxGroups];
+        std::memcpy(chg, c->rpin + RP, 8 * (size_t)G);
+        any = false;
+        for (uint32_t r = 0; r < R; r++) {
+            uint64_t& m = act.m[r >> 6];
+            const uint64_t bit = 1ull << (r & 63u);
+            if (!(m & bit)) continue;
+            c->rep_passes[r] = pass;
+            c->rep_viol[r] = c->rpin[r];
+            if (c->rpin[r] == 0u) {
+                m &= ~bit;
+            } else if (pass >= 2u && !(chg[r >> 6] & bit)) {
+                // a fixed point: the same flags met the same colouring, as they will in every further pass
+                // (pass 1 is excluded: its flags are those of another colouring)
+                c->rep_passes[r] = c->repair_max;
+                m &= ~bit;
+            }
+            any = any || (m & bit);
+        }
+    }
+    MCMC_HIP_TRY(hipEventRecord(c->ev1, c->stream));
+    MCMC_HIP_TRY(hipEventSynchronize(c->ev1));
+    MCMC_HIP_TRY(hipEventElapsedTime(&c->repair_ms, c->ev0, c->ev1));
+    c->hist_valid = false;
+    c->cache_g = -1;
+    c->repaired = true;
+    return MCMC_OK;
+}
 
 // The batch of mcmc_chains_create (specs: nCol, epsilon of `p` and seed + r for every chain; the
 // uniform sweep), of mcmc_chains_create_ladder (the caller's specs; the ladder sweep) and of
@@ -827,7 +995,8 @@ int mcmc_chains_create_wide(const mcmc_graph* g, const mcmc_params* p, const mcm
 
 int mcmc_chains_get_info(mcmc_chains* c, uint64_t out[8]) {
     if (!c || !out) return fail(MCMC_E_ARG, "NULL argument");
-    const uint64_t w[8] = {c->tiled ? 1u : 0u, c->bytes, c->a.vb, c->a.G, chains_grid_x(c->a), c->ladder ? 1u : 0u, c->mw, 0u};
+    const uint64_t w[8] = {c->tiled ? 1u : 0u, c->bytes, c->a.vb, c->a.G, chains_grid_x(c->a), c->ladder ? 1u : 0u, c->mw,
+                           (uint64_t)((double)c->repair_ms * 1000.0 + 0.5)};
     std::memcpy(out, w, sizeof(w));
     return MCMC_OK;
 }
@@ -841,6 +1010,41 @@ int mcmc_chains_set_glibc_windows(mcmc_chains* c, const uint32_t* windows) {
 int mcmc_chains_set_tailcut_repair(mcmc_chains* c, uint32_t max_passes) {
     if (!c) return fail(MCMC_E_ARG, "NULL context");
     if (max_passes) return fail(MCMC_E_ARG, "chains: tail-cut repair is not supported (run the chain with mcmc_run)");
+    return MCMC_OK;
+}
+
+int mcmc_chains_enable_repair(mcmc_chains* c, uint32_t max_passes) {
+    if (!c) return fail(MCMC_E_ARG, "NULL context");
+    if (c->t != 0u) return fail(MCMC_E_ARG, "chains: mcmc_chains_enable_repair after a run has started (the sweeps so far kept no flags)");
+    MCMC_HIP_TRY(hipSetDevice(c->device));
+    c->repair_max = max_passes;
+    if (!max_passes || c->rmem) return MCMC_OK;
+    const ChainArgs& a = c->a;
+    const size_t n = a.n, G = a.G, RP = G * kLanes;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_vfl = up(16 * n * G), b_fl = up(8 * n * G), b_list = up(4 * n * G), b_len = up(4 * G),
+                 b_cidx = up(256 * RP), b_cnt = up(4 * RP + 8 * G);
+    const size_t need = b_vfl + b_fl + b_list + b_len + b_cidx + b_cnt;
+    hipError_t e = hipMalloc(&c->rmem, need);
+    if (e == hipSuccess) e = hipMemset(c->rmem, 0, need);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&c->rpin), 4 * RP + 8 * G);
+    if (e != hipSuccess) {
+        if (c->rmem) (void)hipFree(c->rmem);
+        c->rmem = nullptr;
+        c->repair_max = 0;
+        return fail(e == hipErrorOutOfMemory ? MCMC_E_NOMEM : MCMC_E_HIP,
+                    std::string("chains: tail-cut repair needs ") + std::to_string(need) + " bytes: " + hipGetErrorString(e));
+    }
+    uint8_t* at = static_cast<uint8_t*>(c->rmem);
+    auto take = [&](size_t b) { uint8_t* q = at; at += b; return q; };
+    c->a.vfl = reinterpret_cast<uint64_t*>(take(b_vfl));
+    c->ta.fl = reinterpret_cast<uint64_t*>(take(b_fl));
+    c->ta.list = reinterpret_cast<uint32_t*>(take(b_list));
+    c->ta.listlen = reinterpret_cast<uint32_t*>(take(b_len));
+    c->ta.cidx = take(b_cidx);
+    c->ta.cnt = reinterpret_cast<uint32_t*>(take(b_cnt));
+    c->ta.chg = reinterpret_cast<uint64_t*>(c->ta.cnt + RP);   // 4 RP is a multiple of 8
+    c->rbytes = need;
     return MCMC_OK;
 }
 
@@ -875,22 +1079,10 @@ int mcmc_chains_run(mcmc_chains* c, uint32_t max_sweeps, mcmc_run_stats* stats) 
         const uint32_t b = std::min(kPollSweeps, total - k);
         for (uint32_t j = 0; j < b; j++, c->t++) {
             const uint32_t tn = (uint32_t)(((uint64_t)c->t * a.n) % kMinstdN);
-            if (c->mw == 8u && c->tiled)
-                chains_sweep_wide_kernel<true, 8><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
-            else if (c->mw == 8u)
-                chains_sweep_wide_kernel<false, 8><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
-            else if (c->mw == 4u && c->tiled)
-                chains_sweep_wide_kernel<true, 4><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
-            else if (c->mw == 4u)
-                chains_sweep_wide_kernel<false, 4><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
-            else if (c->tiled && c->ladder)
-                chains_sweep_kernel<true, true><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
-            else if (c->tiled)
-                chains_sweep_kernel<true, false><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
-            else if (c->ladder)
-                chains_sweep_kernel<false, true><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+            if (c->repair_max)
+                chains_launch_sweep<true>(c, grid, tn);
             else
-                chains_sweep_kernel<false, false><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
+                chains_launch_sweep<false>(c, grid, tn);
             chains_commit_kernel<<<a.R, 64, 0, c->stream>>>(a, c->t);
         }
         MCMC_HIP_TRY(hipGetLastError());
@@ -905,6 +1097,13 @@ int mcmc_chains_run(mcmc_chains* c, uint32_t max_sweeps, mcmc_run_stats* stats) 
     MCMC_HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     int rc = chains_sync_state(c);
     if (rc) return rc;
+    // the tail cut, once, after the run in which the last chain stopped (a run cut short by max_sweeps
+    // repairs nothing); loopMs stays the sweep loop's time
+    if (c->repair_max && !c->repaired &&
+        std::all_of(c->st.begin(), c->st.end(), [](const ChainState& h) { return h.done != 0u; })) {
+        rc = chains_repair(c);
+        if (rc) return rc;
+    }
     for (uint32_t r = 0; r < a.R; r++) {
         const ChainState& h = c->st[r];
         if (!stats) break;
@@ -917,6 +1116,10 @@ int mcmc_chains_run(mcmc_chains* c, uint32_t max_sweeps, mcmc_run_stats* stats) 
         s.initDraws = c->init_draws[r];
         s.loopMs = ms;
         s.sweepsRun = h.iter + (h.done ? 1u : 0u);
+        if (c->repaired) {
+            s.finalViol = c->rep_viol[r];
+            s.tailcutPasses = c->rep_passes[r];
+        }
         stats[r] = s;
     }
     return MCMC_OK;
@@ -950,23 +1153,7 @@ int mcmc_chains_get_histograms_n(mcmc_chains* c, uint32_t* out, uint32_t cols) {
     MCMC_HIP_TRY(hipSetDevice(c->g->g.device));
     const ChainArgs& a = c->a;
     const uint32_t hc = c->hist_cols();
-    if (!c->hist_valid) {   // computed on demand, kept until the next run
-        // vertices per workgroup: 1024, more once that makes over ~1024 workgroups per group (each
-        // flushes up to 64 x nCol cells); a multiple of the 32 a wave takes per turn
-        uint32_t hv = (std::max(1024u, (uint32_t)(((uint64_t)a.n + 1023u) / 1024u)) + 31u) & ~31u;
-        if (hc == 256u) hv = std::min(hv, kHistWideMaxV);
-        const dim3 grid((a.n + hv - 1u) / hv, a.G);
-        MCMC_HIP_TRY(hipMemsetAsync(a.hist, 0, 4 * (size_t)hc * a.G * kLanes, c->stream));
-        if (hc == 256u)
-            chains_hist_wide_kernel<<<grid, 64 * kHistWideWaves, 0, c->stream>>>(a, c->t, hv);
-        else
-            chains_hist_kernel<<<grid, 64 * kHistWaves, 0, c->stream>>>(a, c->t, hv);
-        MCMC_HIP_TRY(hipGetLastError());
-        c->hist.resize((size_t)a.R * hc);
-        MCMC_HIP_TRY(hipMemcpyAsync(c->hist.data(), a.hist, 4 * c->hist.size(), hipMemcpyDeviceToHost, c->stream));
-        MCMC_HIP_TRY(hipStreamSynchronize(c->stream));
-        c->hist_valid = true;
-    }
+    if (int rc = chains_histograms(c)) return rc;
     const uint32_t k = std::min(cols, hc);   // columns past the kernel's row are colours no chain has
     for (uint32_t r = 0; r < a.R; r++) {
         std::memcpy(out + (size_t)r * cols, c->hist.data() + (size_t)r * hc, 4 * (size_t)k);
@@ -1008,6 +1195,8 @@ void mcmc_chains_destroy(mcmc_chains* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->mem) (void)hipFree(c->mem);
+    if (c->rmem) (void)hipFree(c->rmem);
+    if (c->rpin) (void)hipHostFree(c->rpin);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);

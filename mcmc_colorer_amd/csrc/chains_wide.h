@@ -76,8 +76,8 @@ __device__ __forceinline__ void drain_chunk_wide(const uint32_t* __restrict__ Cw
 
 // TILED as in chains_sweep_kernel. MW: 32-bit words of a chain's occupancy (4: every nCol <= 128,
 // 8: <= 256). Always "ladder style": nCol, epsilon, hi, full, fr, ps and the walk's end are per lane
-// (a.ncolw, a.epsr).
-template <bool TILED, int MW>
+// (a.ncolw, a.epsr). FLAGS as in chains_sweep_kernel.
+template <bool TILED, int MW, bool FLAGS>
 __global__ __launch_bounds__(64 * kSweepWaves) void chains_sweep_wide_kernel(ChainArgs a, uint32_t t, uint32_t tn) {
     if (*a.ndone >= a.R) return;   // every chain stopped (workgroup-uniform)
     __shared__ uint32_t s_viol[kLanes];
@@ -224,6 +224,11 @@ __global__ __launch_bounds__(64 * kSweepWaves) void chains_sweep_wide_kernel(Cha
             }
             const bool viol = (ownw >> (c & 31u)) & 1u;
             nviol += (live && viol) ? 1u : 0u;
+            if constexpr (FLAGS) {
+                const uint64_t fb = __ballot(viol);
+                uint64_t* fw = a.vfl + ((size_t)(t & 1u) * a.G + g) * n + v;
+                if (lane == 0u) *fw = (*fw & ~livemask) | (fb & livemask);
+            }
             uint32_t tb = tab ? tab[(size_t)v * kLanes + lane] : 0u;
             uint32_t newc = c;
             bool ovf = false;

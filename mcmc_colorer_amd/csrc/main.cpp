@@ -226,10 +226,10 @@ int main(int argc, char** argv) {
         std::cout << "No coloring algorithm specified: enabling MCMC GPU (--mcmcgpu)" << std::endl;
         mcmcgpu = true;
     }
-    if (chains && (repetSet || gpus > 1 || !mcmcgpu || mcmccpu || greedyff || lubygpu || vffgpu || tailcutRepair ||
+    if (chains && (repetSet || gpus > 1 || !mcmcgpu || mcmccpu || greedyff || lubygpu || vffgpu ||
                    chains > 1024 || nCol > 256)) {
-        std::cout << "--chains R batches --mcmcgpu alone: 1 <= R <= 1024, --nCol <= 256, no --repet, --gpus > 1, "
-                     "--tailcutRepair or other colorer" << std::endl;
+        std::cout << "--chains R batches --mcmcgpu alone: 1 <= R <= 1024, --nCol <= 256, no --repet, --gpus > 1 "
+                     "or other colorer" << std::endl;
         return 255;
     }
     if (ladderLo && (!chains || nCol || chains % (ladderHi - ladderLo + 1))) {
@@ -334,15 +334,20 @@ int main(int argc, char** argv) {
                              : new Chains(Chains::Wide{}, g, GPURandGen.randStates, params, chains))
                  : (ladderLo ? new Chains(g, params, specs) : new Chains(g, GPURandGen.randStates, params, chains)));
         ColoringMCMCChains<float, float>& batch = *bp;
+        if (tailcutRepair) batch.setRepair(1000u);   // as the single path
         batch.run();
         uint64_t sweeps = 0;
         for (uint32_t r = 0; r < chains; r++) {
             batch.save(r, outDir + "/" + graphName + "-MCMC_GPU-" + std::to_string(r));
             sweeps += batch.getStats(r).iter;
+            if (tailcutRepair)
+                std::cout << "chain " << r << ": " << batch.getStats(r).tailcutPasses << " tail-cut passes, final conflicts "
+                          << batch.getStats(r).finalViol << std::endl;
         }
         std::cout << "MCMC GPU chains elapsed time: " << batch.getStats(0).loopMs / 1000.0 << " (" << chains
                   << " chains, " << sweeps << " chain-sweeps, rows from the "
                   << (batch.info()[0] ? "tiled layout" : "CSR") << ")" << std::endl;
+        if (tailcutRepair) std::cout << "tail-cut repair: " << batch.info()[7] / 1000.0 << " ms" << std::endl;
         if (ladderLo) {
             const int best = batch.summary(std::cout);
             if (best < 0)
