@@ -377,6 +377,14 @@ public:
     ColoringMCMCChains(Wide, Graph<nodeW, edgeW>* inGraph_d, ColoringMCMCParams params, std::vector<mcmc_chain_spec> ladder)
         : graph(inGraph_d), seed(ladder.empty() ? 0u : ladder[0].seed), param(params), R((uint32_t)ladder.size()),
           specs(std::move(ladder)), wide(true) {}
+    // The half-word batch (mcmc_chains_create_wide16): per-chain nCol up to 2048, 16-bit colours; no setRepair.
+    struct Wide16 {};
+    ColoringMCMCChains(Wide16, Graph<nodeW, edgeW>* inGraph_d, GPURandHandle* randStates, ColoringMCMCParams params,
+                       uint32_t chains)
+        : graph(inGraph_d), seed(randStates->seed), param(params), R(chains), wide16(true) {}
+    ColoringMCMCChains(Wide16, Graph<nodeW, edgeW>* inGraph_d, ColoringMCMCParams params, std::vector<mcmc_chain_spec> ladder)
+        : graph(inGraph_d), seed(ladder.empty() ? 0u : ladder[0].seed), param(params), R((uint32_t)ladder.size()),
+          specs(std::move(ladder)), wide16(true) {}
     ColoringMCMCChains(const ColoringMCMCChains&) = delete;
     ColoringMCMCChains& operator=(const ColoringMCMCChains&) = delete;
     ~ColoringMCMCChains() { mcmc_chains_destroy(ctx); }
@@ -398,7 +406,9 @@ public:
         p.tabooIteration = param.tabooIteration;
         p.tailcut = param.tailcut;
         p.seed = seed;
-        if (wide)
+        if (wide16)
+            MCMC_CHECK(mcmc_chains_create_wide16(graph->handle(), &p, specs.empty() ? nullptr : specs.data(), R, &ctx));
+        else if (wide)
             MCMC_CHECK(mcmc_chains_create_wide(graph->handle(), &p, specs.empty() ? nullptr : specs.data(), R, &ctx));
         else if (specs.empty())
             MCMC_CHECK(mcmc_chains_create(graph->handle(), &p, R, &ctx));   // a generated graph: its tiled layout, no CSR
@@ -430,7 +440,7 @@ public:
         return specs.empty() ? mcmc_chain_spec{param.nCol, seed + r, param.epsilon, 0u} : specs.at(r);
     }
     // [chains][cols] class sizes of every chain's colouring, counted on the device; cols >= the largest
-    // nCol (64 serves every narrow batch, 256 every batch)
+    // nCol (64 serves every narrow batch, 256 every wide one, 2048 every batch)
     std::vector<uint32_t> histograms(uint32_t cols = 64) const {
         std::vector<uint32_t> h((size_t)R * cols);
         MCMC_CHECK(mcmc_chains_get_histograms_n(ctx, h.data(), cols));
@@ -442,7 +452,7 @@ public:
     // smallest nCol, then the smallest deviation, then the lowest index; -1 if there is none. Host code
     // over the device histograms.
     int summary(std::ostream& out) const {
-        const uint32_t cols = wide ? 256u : 64u;
+        const uint32_t cols = wide16 ? 2048u : wide ? 256u : 64u;
         const std::vector<uint32_t> h = histograms(cols);
         int best = -1;
         double bestStd = 0;
@@ -538,6 +548,7 @@ private:
     uint32_t R;
     std::vector<mcmc_chain_spec> specs;   // a ladder's; empty: uniform
     bool wide{false};                     // mcmc_chains_create_wide
+    bool wide16{false};                   // mcmc_chains_create_wide16
     uint32_t repair{0};                   // mcmc_chains_enable_repair's max_passes
     mcmc_chains* ctx{nullptr};
     std::vector<mcmc_run_stats> stats;

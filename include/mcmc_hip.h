@@ -294,10 +294,24 @@ int mcmc_chains_create_ladder(const mcmc_graph* g, const mcmc_params* p, const m
  * bit for bit, the single run with its own (nCol, epsilon, seed). */
 int mcmc_chains_create_wide(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_spec* specs /* may be NULL */,
                             uint32_t R, mcmc_chains** out);
+/* The half-word batch: per-chain 2 <= nCol <= 2048, colours stored as 16-bit (csrc/chains_wide16.h), so
+ * that a batch reaches the reference's default nCol = maxDeg and the range of the wide single run. The
+ * sweep keeps a chain's occupancy in 16 (every nCol <= 512), 32 (<= 1024) or 64 words of a wave-private
+ * LDS table, counts newly set bits while it drains a row, and walks the CDF over runs and binades
+ * (csrc/cdf_walk.h) -- always, also when every nCol is small. specs == NULL: a uniform batch;
+ * otherwise a ladder. 2 <= nCol <= 2048 and reserved == 0, else MCMC_E_ARG naming the chain; every other
+ * rule is mcmc_chains_create_wide's, with 4 n 64 ceil(R / 64) bytes of colours. Chain r is, bit for
+ * bit, the single run with its own (nCol, epsilon, seed). Class sizes: mcmc_chains_get_histograms_n
+ * with cols >= the largest nCol (the device counts 512, 1024 or 2048 colours per chain; at most 65504
+ * vertices per workgroup in packed 16-bit counters, exact). mcmc_chains_enable_repair(max_passes > 0)
+ * on such a batch is MCMC_E_ARG: the batched tail cut reads byte colours. */
+int mcmc_chains_create_wide16(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_spec* specs /* may be NULL */,
+                              uint32_t R, mcmc_chains** out);
 /* out[0] adjacency source of the sweep (0 CSR, 1 tiled layout), [1] device bytes of the batch's own
  * allocation, [2] vertices per wave, [3] chain groups, [4] sweep grid x, [5] 1 for a ladder
- * (mcmc_chains_create_ladder, mcmc_chains_create_wide), else 0, [6] mask words of the sweep: 0 for
- * the narrow kernels, 4 or 8 for the wide one, [7] the tail-cut repair's time on the stream in
+ * (mcmc_chains_create_ladder, mcmc_chains_create_wide, _wide16), else 0, [6] mask words of the sweep: 0 for
+ * the narrow kernels, 4 or 8 for the wide one, 16, 32 or 64 for the half-word one (whose workgroups
+ * are 4, 4 and 2 waves: [4] counts them), [7] the tail-cut repair's time on the stream in
  * microseconds (hipEvent; 0 until mcmc_chains_enable_repair's repair ran). */
 int mcmc_chains_get_info(mcmc_chains* c, uint64_t out[8]);
 /* windows[R][31]; default: every chain at srand(1) with no draws (mcmc_set_glibc_window's default).

@@ -67,6 +67,7 @@ SIGNATURES: dict[str, tuple] = {
     "mcmc_chains_create": (c_int, [c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
     "mcmc_chains_create_ladder": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
     "mcmc_chains_create_wide": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
+    "mcmc_chains_create_wide16": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
     "mcmc_chains_get_histograms": (c_int, [c_void_p, _u32p]),
     "mcmc_chains_get_histograms_n": (c_int, [c_void_p, _u32p, c_uint32]),
     "mcmc_chains_get_info": (c_int, [c_void_p, _u64p]),

@@ -369,28 +369,33 @@ class ColoringMCMCChains:
     ``ColoringMCMCChains.ladder`` gives every chain its own nCol, epsilon and seed; ``histograms()``,
     ``summary()`` and ``best()`` compare the chains from class sizes counted on the device.
     ``wide=True`` (here and in ``ladder``) runs the wide sweep, mcmc_chains_create_wide: 2 <= nCol <=
-    256 per chain, the occupancy masks in LDS; ``histograms()`` then has 256 columns."""
+    256 per chain, the occupancy masks in LDS; ``histograms()`` then has 256 columns.
+    ``wide16=True`` (not with ``wide``) runs the half-word sweep, mcmc_chains_create_wide16: 2 <= nCol <=
+    2048 per chain, 16-bit colours; ``histograms()`` then has as many columns as the largest nCol, and
+    ``repair > 0`` raises the library's error."""
 
     def __init__(self, graph: Graph, params: ColoringMCMCParams, seed: int, chains: int, glibc=None, specs=None,
-                 wide: bool = False, repair: int = 0):
+                 wide: bool = False, repair: int = 0, wide16: bool = False):
+        if wide and wide16:
+            raise ValueError("wide and wide16 are mutually exclusive")
         if params.nCol == 0 and specs is None:
             params = ColoringMCMCParams(**{**params.__dict__, "nCol": default_ncol(graph, params)})
         self.graph, self.param, self.seed, self.chains = graph, params, seed, int(chains)
         self._h = ctypes.c_void_p()
         self._cparams = params.to_c(seed)
-        self.wide = bool(wide)
+        self.wide, self.wide16 = bool(wide), bool(wide16)
+        create_w = lib().mcmc_chains_create_wide16 if wide16 else lib().mcmc_chains_create_wide
         if specs is None:   # uniform: every chain params.nCol, params.epsilon, seed + r
             self.specs = [(params.nCol, float(np.float32(params.epsilon)), (seed + r) & 0xFFFFFFFF)
                           for r in range(self.chains)]
-            if wide:
-                check(lib().mcmc_chains_create_wide(graph.handle, ctypes.byref(self._cparams), None, self.chains,
-                                                    ctypes.byref(self._h)))
+            if wide or wide16:
+                check(create_w(graph.handle, ctypes.byref(self._cparams), None, self.chains, ctypes.byref(self._h)))
             else:
                 check(lib().mcmc_chains_create(graph.handle, ctypes.byref(self._cparams), self.chains, ctypes.byref(self._h)))
         else:
             self.specs = [(int(k), float(np.float32(e)), int(s) & 0xFFFFFFFF) for k, e, s in specs]
             arr = (MCMCChainSpec * self.chains)(*[MCMCChainSpec(k, s, e, 0) for k, e, s in self.specs])
-            create = lib().mcmc_chains_create_wide if wide else lib().mcmc_chains_create_ladder
+            create = create_w if wide or wide16 else lib().mcmc_chains_create_ladder
             check(create(graph.handle, ctypes.byref(self._cparams), arr, self.chains, ctypes.byref(self._h)))
         check(lib().mcmc_chains_set_tailcut_repair(self._h, int(params.tailcutRepair)))
         if repair:
@@ -402,14 +407,14 @@ class ColoringMCMCChains:
 
     @classmethod
     def ladder(cls, graph: Graph, params: ColoringMCMCParams, specs, glibc=None, wide: bool = False,
-               repair: int = 0) -> "ColoringMCMCChains":
-        """One batch whose chain r has its own ``specs[r] = (nCol, epsilon, seed)`` (2 <= nCol <= 64, or
-        <= 256 with ``wide=True``): mcmc_chains_create_ladder / mcmc_chains_create_wide. ``params``
+               repair: int = 0, wide16: bool = False) -> "ColoringMCMCChains":
+        """One batch whose chain r has its own ``specs[r] = (nCol, epsilon, seed)`` (2 <= nCol <= 64, <= 256
+        with ``wide=True``, <= 2048 with ``wide16=True``): mcmc_chains_create_ladder / _wide / _wide16. ``params``
         supplies maxRip, tabooIteration and tailcut; its nCol and epsilon are ignored. Chain r equals the
         single run with its own three values, bit for bit."""
         specs = list(specs)
         return cls(graph, params, specs[0][2] if specs else 0, len(specs), glibc=glibc, specs=specs, wide=wide,
-                   repair=repair)
+                   repair=repair, wide16=wide16)
 
     def run(self, max_sweeps: int = 0) -> list[MCMCRunStats]:
         w = np.ascontiguousarray(np.stack([g.window for g in self.glibc]), dtype=np.uint32)
@@ -429,17 +434,19 @@ class ColoringMCMCChains:
     def info(self) -> list[int]:
         """mcmc_chains_get_info: [adjacency source (0 CSR, 1 tiled layout), device bytes of the batch,
         vertices per wave, chain groups, sweep grid x, 1 for a ladder, mask words of the sweep (0 narrow,
-        4 or 8 wide), microseconds of the tail-cut repair]."""
+        4 or 8 wide, 16, 32 or 64 half-word), microseconds of the tail-cut repair]."""
         out = np.zeros(8, dtype=np.uint64)
         check(lib().mcmc_chains_get_info(self._h, u64ptr(out)))
         return [int(x) for x in out]
 
     def histograms(self) -> np.ndarray:
-        """[chains][64] ([chains][256] for a wide batch) class sizes of every chain's colouring, counted
-        on the device (mcmc_chains_get_histograms / _n): no colouring is copied to the host."""
-        out = np.zeros((self.chains, 256 if self.wide else 64), dtype=np.uint32)
-        if self.wide:
-            check(lib().mcmc_chains_get_histograms_n(self._h, u32ptr(out), 256))
+        """[chains][64] ([chains][256] for a wide batch, [chains][largest nCol] for a half-word one) class
+        sizes of every chain's colouring, counted on the device (mcmc_chains_get_histograms / _n): no
+        colouring is copied to the host."""
+        cols = max(k for k, _, _ in self.specs) if self.wide16 else 256 if self.wide else 64
+        out = np.zeros((self.chains, cols), dtype=np.uint32)
+        if self.wide or self.wide16:
+            check(lib().mcmc_chains_get_histograms_n(self._h, u32ptr(out), cols))
         else:
             check(lib().mcmc_chains_get_histograms(self._h, u32ptr(out)))
         return out

@@ -70,6 +70,11 @@
 //   64 distinct columns per instruction, and read back by the chain's lane. The sweeps above are
 //   untouched: they read the byte table a.ncol, the wide sweep and the commit the 16-bit a.ncolw.
 //   Batches above 64 colours count their class sizes with chains_hist_wide_kernel (rows of 256).
+// Wide16 (mcmc_chains_create_wide16, chains_wide16.h): per-chain nCol up to 2048, colours as uint16_t
+//   (C16[buffer][group][v][64]). chains_sweep_wide16_kernel<TILED, MW> has MW = 16, 32 or 64 table words per
+//   chain, counts newly set bits with the returning ds_or so that a chain's Zv is one LDS word, and walks
+//   the CDF with cdf_walk.h per lane. The init and commit kernels are templates over the colour element;
+//   class sizes come from chains_hist16_kernel; the tail cut is refused for such a batch.
 // Tail cut (mcmc_chains_enable_repair, chains_tailcut.h): after the loop every chain that stopped with
 //   violators is repaired as the single run's corrected tail cut repairs it, 64 chains per row read; the
 //   sweeps' FLAGS instantiations keep the violator ballots its first pass needs.
@@ -84,6 +89,7 @@
 #include <string>
 #include <vector>
 
+#include "cdf_walk.h"
 #include "mcmc_common.h"
 #include "rng.h"
 
@@ -113,7 +119,7 @@ struct ChainArgs {
     uint32_t n, R, G, nCol, vb;
     uint32_t taboo_it, z, maxRip, traj_cap;
     float eps;
-    uint8_t* C[2];          // [G][n][64]
+    uint8_t* C[2];          // [G][n][64] bytes; uint16_t elements in a half-word batch (chains_wide16.h)
     uint32_t* taboo;        // [G][n][64], nullptr when tabooIteration == 0
     uint32_t* xinit;        // [G * 64] engine state after the initial colouring
     uint64_t* init_draws;   // [G * 64]
@@ -129,8 +135,8 @@ struct ChainArgs {
     // instantiations of the sweep, the commit's rand() % (nCol_r - 1)
     const uint8_t* ncol;    // [G * 64], 0 past R (the narrow ladder sweeps; a wide batch's entries are not read)
     const float* epsr;      // [G * 64]
-    uint32_t* hist;         // [G * 64][64 or 256] class sizes of the final colourings (chains_hist_kernel / _wide_)
-    const uint16_t* ncolw;  // [G * 64], 0 past R: nCol up to 256 (the wide sweeps, the commit)
+    uint32_t* hist;         // [G * 64][64 or 256] class sizes of the final colourings (chains_hist_kernel / _wide_); rows of 512, 1024 or 2048 in a half-word batch
+    const uint16_t* ncolw;  // [G * 64], 0 past R: nCol up to 2048 (the wide and half-word sweeps, the commit)
     uint64_t* vfl;          // [2][G][n] violator ballots of sweep t in vfl[t & 1] (the FLAGS sweeps; chains_tailcut.h)
 };
 
@@ -427,6 +433,8 @@ __global__ __launch_bounds__(64 * kSweepWaves) void chains_sweep_kernel(ChainArg
     if (threadIdx.x < kLanes && s_viol[threadIdx.x]) atomicAdd(&a.viol[g * kLanes + threadIdx.x], s_viol[threadIdx.x]);
 }
 
+// CT: the colour element, uint8_t or, for a half-word batch (chains_wide16.h), uint16_t
+template <typename CT>
 __global__ __launch_bounds__(64) void chains_commit_kernel(ChainArgs a, uint32_t t) {
     const uint32_t r = blockIdx.x, lane = threadIdx.x, g = r >> 6, bit = r & 63u;
     ChainState* s = a.st + r;
@@ -453,8 +461,8 @@ __global__ __launch_bounds__(64) void chains_commit_kernel(ChainArgs a, uint32_t
     const uint32_t evc = min(a.evcnt[(t & 1u) * a.G + g], a.n);
     if (evc == 0u) return;
     const size_t gofs = (size_t)g * a.n * kLanes;
-    const uint8_t* Cc = a.C[t & 1u] + gofs;
-    uint8_t* Cn = a.C[(t + 1u) & 1u] + gofs;
+    const CT* Cc = reinterpret_cast<const CT*>(a.C[t & 1u]) + gofs;
+    CT* Cn = reinterpret_cast<CT*>(a.C[(t + 1u) & 1u]) + gofs;
     const uint4* ev = a.evlist + (size_t)g * a.n;
     uint32_t* ring = a.ring + (size_t)r * 31u;
     uint32_t head = s->head, served = 0u;
@@ -471,7 +479,7 @@ __global__ __launch_bounds__(64) void chains_commit_kernel(ChainArgs a, uint32_t
         if (lane == 0u) {
             const uint32_t nc = glibc_next(ring, head) % ((uint32_t)a.ncolw[r] - 1u);   // :518, the chain's own nCol
             const size_t at = (size_t)best * kLanes + bit;
-            Cn[at] = (uint8_t)nc;
+            Cn[at] = (CT)nc;
             if (a.taboo) a.taboo[gofs + at] = (nc == Cc[at]) ? a.taboo_it : 0u;   // :526
         }
         served++;
@@ -486,10 +494,11 @@ __global__ __launch_bounds__(64) void chains_commit_kernel(ChainArgs a, uint32_t
 }
 
 // tab[G * 64]: {the chain's engine seed, its UniformIntConst scaling and past, 0}, built by the host
+template <typename CT>
 __global__ __launch_bounds__(64) void chains_init_kernel(ChainArgs a, const uint4* __restrict__ tab) {
     const uint32_t lane = threadIdx.x, g = blockIdx.x, r = g * kLanes + lane;
     const bool live = r < a.R;
-    uint8_t* C0 = a.C[0] + (size_t)g * a.n * kLanes;
+    CT* C0 = reinterpret_cast<CT*>(a.C[0]) + (size_t)g * a.n * kLanes;
     const uint4 sp = tab[r];
     UniformIntConst k;
     k.scaling = sp.y;
@@ -507,7 +516,7 @@ __global__ __launch_bounds__(64) void chains_init_kernel(ChainArgs a, const uint
             } while (rr >= k.past);
             col = rr / k.scaling;
         }
-        C0[(size_t)v * kLanes + lane] = (uint8_t)col;
+        C0[(size_t)v * kLanes + lane] = (CT)col;
     }
     a.xinit[r] = x;
     a.init_draws[r] = draws;
@@ -579,6 +588,7 @@ __global__ __launch_bounds__(64 * kHistWaves) void chains_hist_kernel(ChainArgs 
 }
 
 #include "chains_wide.h"
+#include "chains_wide16.h"
 #include "chains_tailcut.h"
 
 }  // namespace
@@ -593,7 +603,8 @@ struct mcmc_chains {
     ChainArgs a{};
     bool tiled = false;           // the sweep reads the graph's tiled layout (no CSR), else the CSR
     bool ladder = false;          // mcmc_chains_create_ladder: the per-chain instantiations of the sweep
-    uint32_t mw = 0;              // mcmc_chains_create_wide: mask words of the wide sweep (4 or 8), else 0
+    uint32_t mw = 0;              // mcmc_chains_create_wide / _wide16: mask words of the sweep (4, 8 / 16, 32, 64), else 0
+    uint32_t esz = 1;             // bytes per colour: 2 for mcmc_chains_create_wide16 (chains_wide16.h)
     uint32_t maxncol = 0;         // the batch's largest nCol; above 64 the histogram rows are 256 wide
     std::vector<uint32_t> hist;   // get_histograms: [R][hist_cols()], valid until the next run
     bool hist_valid = false;
@@ -617,14 +628,15 @@ struct mcmc_chains {
     std::vector<uint32_t> rep_passes;   // per chain; empty until the repair ran
     std::vector<uint64_t> rep_viol;
     float repair_ms = 0.0f;
-    uint32_t hist_cols() const { return maxncol > 64u ? 256u : 64u; }
+    uint32_t hist_cols() const { return esz == 2u ? 32u * mw : maxncol > 64u ? 256u : 64u; }
+    uint32_t sweep_waves() const { return esz == 2u ? (uint32_t)wide16_waves((int)mw) : kSweepWaves; }
 };
 
 namespace {
 
-// workgroups of a sweep along x: kSweepWaves waves of vb vertices each
-uint32_t chains_grid_x(const ChainArgs& a) {
-    return (uint32_t)(((uint64_t)a.n + (uint64_t)a.vb * kSweepWaves - 1) / ((uint64_t)a.vb * kSweepWaves));
+// workgroups of a sweep along x: `waves` waves of vb vertices each
+uint32_t chains_grid_x(const ChainArgs& a, uint32_t waves = kSweepWaves) {
+    return (uint32_t)(((uint64_t)a.n + (uint64_t)a.vb * waves - 1) / ((uint64_t)a.vb * waves));
 }
 
 int chains_sync_state(mcmc_chains* c) {
@@ -659,7 +671,20 @@ namespace {
 template <bool FLAGS>
 void chains_launch_sweep(mcmc_chains* c, dim3 grid, uint32_t tn) {
     const ChainArgs& a = c->a;
-    if (c->mw == 8u && c->tiled)
+    if (c->esz == 2u) {   // the half-word batch: no FLAGS instantiations (mcmc_chains_enable_repair refuses it)
+        if (c->mw == 64u && c->tiled)
+            chains_sweep_wide16_kernel<true, 64><<<grid, 64 * wide16_waves(64), 0, c->stream>>>(a, c->t, tn);
+        else if (c->mw == 64u)
+            chains_sweep_wide16_kernel<false, 64><<<grid, 64 * wide16_waves(64), 0, c->stream>>>(a, c->t, tn);
+        else if (c->mw == 32u && c->tiled)
+            chains_sweep_wide16_kernel<true, 32><<<grid, 64 * wide16_waves(32), 0, c->stream>>>(a, c->t, tn);
+        else if (c->mw == 32u)
+            chains_sweep_wide16_kernel<false, 32><<<grid, 64 * wide16_waves(32), 0, c->stream>>>(a, c->t, tn);
+        else if (c->tiled)
+            chains_sweep_wide16_kernel<true, 16><<<grid, 64 * wide16_waves(16), 0, c->stream>>>(a, c->t, tn);
+        else
+            chains_sweep_wide16_kernel<false, 16><<<grid, 64 * wide16_waves(16), 0, c->stream>>>(a, c->t, tn);
+    } else if (c->mw == 8u && c->tiled)
         chains_sweep_wide_kernel<true, 8, FLAGS><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
     else if (c->mw == 8u)
         chains_sweep_wide_kernel<false, 8, FLAGS><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
@@ -686,10 +711,14 @@ int chains_histograms(mcmc_chains* c) {
     // vertices per workgroup: 1024, more once that makes over ~1024 workgroups per group (each
     // flushes up to 64 x nCol cells); a multiple of the 32 a wave takes per turn
     uint32_t hv = (std::max(1024u, (uint32_t)(((uint64_t)a.n + 1023u) / 1024u)) + 31u) & ~31u;
-    if (hc == 256u) hv = std::min(hv, kHistWideMaxV);
+    if (hc >= 256u) hv = std::min(hv, kHistWideMaxV);
     const dim3 grid((a.n + hv - 1u) / hv, a.G);
     MCMC_HIP_TRY(hipMemsetAsync(a.hist, 0, 4 * (size_t)hc * a.G * kLanes, c->stream));
-    if (hc == 256u)
+    if (c->esz == 2u) {   // hc = 512, 1024 or 2048: 32, 16 or 8 chains per workgroup
+        const uint32_t hc_log2 = hc == 2048u ? 11u : hc == 1024u ? 10u : 9u;
+        chains_hist16_kernel<<<dim3(grid.x, a.G * (kLanes >> (14u - hc_log2))), kHist16Threads, 0, c->stream>>>(a, c->t, hv,
+                                                                                                                 hc_log2);
+    } else if (hc == 256u)
         chains_hist_wide_kernel<<<grid, 64 * kHistWideWaves, 0, c->stream>>>(a, c->t, hv);
     else
         chains_hist_kernel<<<grid, 64 * kHistWaves, 0, c->stream>>>(a, c->t, hv);
@@ -803,10 +832,11 @@ int chains_repair(mcmc_chains* c) {
 
 // The batch of mcmc_chains_create (specs: nCol, epsilon of `p` and seed + r for every chain; the
 // uniform sweep), of mcmc_chains_create_ladder (the caller's specs; the ladder sweep) and of
-// mcmc_chains_create_wide (wide: the wide sweep, its mask words from the largest nCol). The
+// mcmc_chains_create_wide (wide: the wide sweep, its mask words from the largest nCol) and of
+// mcmc_chains_create_wide16 (esz = 2: half-word colours, the sweep of chains_wide16.h). The
 // arguments other than the graph are checked by the callers.
 int chains_create(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_spec* specs, uint32_t R, bool ladder,
-                  bool wide, mcmc_chains** out) {
+                  bool wide, uint32_t esz, mcmc_chains** out) {
     const GraphDev& gd = g->g;
     if (gd.n == 0) return fail(MCMC_E_ARG, "chains: empty graph");
     if (gd.partial_rows)
@@ -824,11 +854,13 @@ int chains_create(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_sp
     const uint32_t n = gd.n, G = (R + kLanes - 1) / kLanes, RP = G * kLanes;
     const uint32_t traj_cap = (uint32_t)std::min<uint64_t>((uint64_t)p->maxRip + 2u, kTrajCapMax);
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_col = up((size_t)n * kLanes * G), b_tab = p->tabooIteration ? up(4 * (size_t)n * kLanes * G) : 0;
+    const size_t b_col = up((size_t)n * kLanes * G * esz), b_tab = p->tabooIteration ? up(4 * (size_t)n * kLanes * G) : 0;
     const size_t b_ev = up(sizeof(uint4) * (size_t)n * G), b_traj = up(4 * (size_t)R * traj_cap);
     uint32_t maxncol = 0;
     for (uint32_t r = 0; r < R; r++) maxncol = std::max(maxncol, specs[r].nCol);
-    const size_t b_hist = up(4 * (maxncol > 64u ? 256 : 64) * (size_t)RP);
+    const uint32_t mw = esz == 2u ? (maxncol > 1024u ? 64u : maxncol > 512u ? 32u : 16u)
+                                  : wide ? (maxncol > 128u ? 8u : 4u) : 0u;
+    const size_t b_hist = up(4 * (esz == 2u ? 32u * mw : maxncol > 64u ? 256u : 64u) * (size_t)RP);
     const size_t b_small = up(4 * RP) * 2 + up(8 * RP) + up(4 * 1024) + up(8 * G) + up(sizeof(ChainState) * RP) +
                            up(4 * 31 * (size_t)RP) + 256 + up(RP) + up(4 * RP) + up(sizeof(uint4) * RP) + b_hist + up(2 * RP);
     const size_t need = 2 * b_col + b_tab + b_ev + b_traj + b_small;
@@ -891,7 +923,8 @@ int chains_create(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_sp
     }
     c->tiled = L != nullptr;
     c->ladder = ladder;
-    c->mw = wide ? (maxncol > 128u ? 8u : 4u) : 0u;
+    c->mw = mw;
+    c->esz = esz;
     c->maxncol = maxncol;
     c->bytes = need;
     a.n = n;
@@ -930,7 +963,10 @@ int chains_create(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_sp
     if (e == hipSuccess) e = hipMemcpy(d_eps, h_eps.data(), 4 * (size_t)RP, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_itab, h_itab.data(), sizeof(uint4) * (size_t)RP, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        chains_init_kernel<<<G, 64, 0, c->stream>>>(a, d_itab);
+        if (esz == 2u)
+            chains_init_kernel<uint16_t><<<G, 64, 0, c->stream>>>(a, d_itab);
+        else
+            chains_init_kernel<uint8_t><<<G, 64, 0, c->stream>>>(a, d_itab);
         e = hipGetLastError();
     }
     c->init_draws.resize(RP);
@@ -958,7 +994,7 @@ int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mc
     if (R < 1 || R > kMaxChains) return fail(MCMC_E_ARG, "chains: 1 <= R <= 1024, got " + std::to_string(R));
     std::vector<mcmc_chain_spec> specs(R);
     for (uint32_t r = 0; r < R; r++) specs[r] = mcmc_chain_spec{p->nCol, p->seed + r, p->epsilon, 0u};
-    return chains_create(g, p, specs.data(), R, false, false, out);
+    return chains_create(g, p, specs.data(), R, false, false, 1u, out);
 }
 
 int mcmc_chains_create_ladder(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_spec* specs, uint32_t R,
@@ -973,7 +1009,7 @@ int mcmc_chains_create_ladder(const mcmc_graph* g, const mcmc_params* p, const m
         if (specs[r].reserved != 0)
             return fail(MCMC_E_ARG, "chains: chain " + std::to_string(r) + ": reserved must be 0");
     }
-    return chains_create(g, p, specs, R, true, false, out);
+    return chains_create(g, p, specs, R, true, false, 1u, out);
 }
 
 int mcmc_chains_create_wide(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_spec* specs, uint32_t R,
@@ -990,12 +1026,29 @@ int mcmc_chains_create_wide(const mcmc_graph* g, const mcmc_params* p, const mcm
         if (sp[r].reserved != 0)
             return fail(MCMC_E_ARG, "chains: chain " + std::to_string(r) + ": reserved must be 0");
     }
-    return chains_create(g, p, sp.data(), R, true, true, out);
+    return chains_create(g, p, sp.data(), R, true, true, 1u, out);
+}
+
+int mcmc_chains_create_wide16(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_spec* specs, uint32_t R,
+                              mcmc_chains** out) {
+    if (!g || !p || !out) return fail(MCMC_E_ARG, "NULL argument");
+    *out = nullptr;
+    if (R < 1 || R > kMaxChains) return fail(MCMC_E_ARG, "chains: 1 <= R <= 1024, got " + std::to_string(R));
+    std::vector<mcmc_chain_spec> sp(R);
+    for (uint32_t r = 0; r < R; r++) {
+        sp[r] = specs ? specs[r] : mcmc_chain_spec{p->nCol, p->seed + r, p->epsilon, 0u};
+        if (sp[r].nCol < 2 || sp[r].nCol > 2048)
+            return fail(MCMC_E_ARG, "chains: chain " + std::to_string(r) + ": 2 <= nCol <= 2048 (the half-word sweep's "
+                                    "occupancy table), got " + std::to_string(sp[r].nCol));
+        if (sp[r].reserved != 0)
+            return fail(MCMC_E_ARG, "chains: chain " + std::to_string(r) + ": reserved must be 0");
+    }
+    return chains_create(g, p, sp.data(), R, true, true, 2u, out);
 }
 
 int mcmc_chains_get_info(mcmc_chains* c, uint64_t out[8]) {
     if (!c || !out) return fail(MCMC_E_ARG, "NULL argument");
-    const uint64_t w[8] = {c->tiled ? 1u : 0u, c->bytes, c->a.vb, c->a.G, chains_grid_x(c->a), c->ladder ? 1u : 0u, c->mw,
+    const uint64_t w[8] = {c->tiled ? 1u : 0u, c->bytes, c->a.vb, c->a.G, chains_grid_x(c->a, c->sweep_waves()), c->ladder ? 1u : 0u, c->mw,
                            (uint64_t)((double)c->repair_ms * 1000.0 + 0.5)};
     std::memcpy(out, w, sizeof(w));
     return MCMC_OK;
@@ -1016,6 +1069,9 @@ int mcmc_chains_set_tailcut_repair(mcmc_chains* c, uint32_t max_passes) {
 int mcmc_chains_enable_repair(mcmc_chains* c, uint32_t max_passes) {
     if (!c) return fail(MCMC_E_ARG, "NULL context");
     if (c->t != 0u) return fail(MCMC_E_ARG, "chains: mcmc_chains_enable_repair after a run has started (the sweeps so far kept no flags)");
+    if (max_passes && c->esz == 2u)
+        return fail(MCMC_E_ARG, "chains: the batched tail cut reads byte colours: a half-word batch "
+                                "(mcmc_chains_create_wide16) has no repair");
     MCMC_HIP_TRY(hipSetDevice(c->device));
     c->repair_max = max_passes;
     if (!max_passes || c->rmem) return MCMC_OK;
@@ -1068,7 +1124,7 @@ int mcmc_chains_run(mcmc_chains* c, uint32_t max_sweeps, mcmc_run_stats* stats) 
     const uint64_t cap = (uint64_t)a.maxRip + 2u;
     const uint64_t left = cap > c->t ? cap - c->t : 0u;
     const uint32_t total = (uint32_t)(max_sweeps ? std::min<uint64_t>(max_sweeps, left) : left);
-    const dim3 grid(chains_grid_x(a), a.G);
+    const dim3 grid(chains_grid_x(a, c->sweep_waves()), a.G);
     c->cache_g = -1;
     c->hist_valid = false;
     MCMC_HIP_TRY(hipEventRecord(c->ev0, c->stream));
@@ -1083,7 +1139,10 @@ int mcmc_chains_run(mcmc_chains* c, uint32_t max_sweeps, mcmc_run_stats* stats) 
                 chains_launch_sweep<true>(c, grid, tn);
             else
                 chains_launch_sweep<false>(c, grid, tn);
-            chains_commit_kernel<<<a.R, 64, 0, c->stream>>>(a, c->t);
+            if (c->esz == 2u)
+                chains_commit_kernel<uint16_t><<<a.R, 64, 0, c->stream>>>(a, c->t);
+            else
+                chains_commit_kernel<uint8_t><<<a.R, 64, 0, c->stream>>>(a, c->t);
         }
         MCMC_HIP_TRY(hipGetLastError());
         k += b;
@@ -1136,12 +1195,18 @@ int mcmc_chains_get_coloring(mcmc_chains* c, uint32_t r, uint32_t* out) {
     }
     const int g = (int)(r / kLanes), buf = (int)c->st[r].buf;
     if (g != c->cache_g || buf != c->cache_buf) {   // one download serves the group's chains
-        c->cache.resize((size_t)n * kLanes);
-        MCMC_HIP_TRY(hipMemcpy(c->cache.data(), c->a.C[buf] + (size_t)g * n * kLanes, c->cache.size(), hipMemcpyDeviceToHost));
+        c->cache.resize((size_t)n * kLanes * c->esz);
+        MCMC_HIP_TRY(hipMemcpy(c->cache.data(), c->a.C[buf] + (size_t)g * n * kLanes * c->esz, c->cache.size(),
+                               hipMemcpyDeviceToHost));
         c->cache_g = g;
         c->cache_buf = buf;
     }
-    for (uint32_t v = 0; v < n; v++) out[v] = c->cache[(size_t)v * kLanes + (r % kLanes)];
+    if (c->esz == 2u) {
+        const uint16_t* h = reinterpret_cast<const uint16_t*>(c->cache.data());
+        for (uint32_t v = 0; v < n; v++) out[v] = h[(size_t)v * kLanes + (r % kLanes)];
+    } else {
+        for (uint32_t v = 0; v < n; v++) out[v] = c->cache[(size_t)v * kLanes + (r % kLanes)];
+    }
     return MCMC_OK;
 }
 

@@ -10,8 +10,10 @@
 //   --tailcutRepair: after the loop, run the reference's tail cut (coloringMCMC_CPU.cpp:272-311)
 //   with its inner loop fixed (k++; the reference's never returns), at most 1000 passes
 //   --chains R: with --mcmcgpu, seeds seed .. seed + R - 1 as one batch (csrc/chains.hip), each chain on
-//   its own copy of the glibc stream; writes the files --repet R names. nCol in 65..256 (here or as
-//   the ladder's HI) runs the wide batch (mcmc_chains_create_wide), nCol <= 64 the narrow one
+//   its own copy of the glibc stream; writes the files --repet R names. nCol (from --nCol, the ladder's
+//   HI, or the reference's default maxDeg / numColRatio) in 257..2048 runs the half-word batch
+//   (mcmc_chains_create_wide16; not with --tailcutRepair), in 65..256 the wide batch
+//   (mcmc_chains_create_wide), nCol <= 64 the narrow one
 //   --nColLadder LO:HI: with --chains R (a multiple of K = HI - LO + 1), chain r has nCol LO + r % K and
 //   seed seed + r / K (one batch, the ladder sweep); one summary line per chain and a `best:` line
 // Outputs <outDir>/<graphName>-MCMC_GPU-<i>.log and -colors.txt per repetition.
@@ -127,11 +129,13 @@ void help(const char* argv0) {
               << "  --tailcutRepair      then repair the remaining conflicts (corrected tail cut, <= 1000 passes)\n"
               << "  --repet N            repetitions, seeds seed+i (default 1)\n"
               << "  --chains R           --mcmcgpu: seeds seed .. seed+R-1 as ONE batch, a wave lane per chain\n"
-              << "                       (nCol <= 256, above 64 the wide sweep; R <= 1024; each chain its own glibc\n"
-              << "                       stream; not with --repet / --gpus)\n"
+              << "                       (nCol <= 2048: above 64 the wide sweep, above 256 the half-word sweep, which\n"
+              << "                       has no --tailcutRepair; R <= 1024; each chain its own glibc stream; not with\n"
+              << "                       --repet / --gpus)\n"
               << "  --nColLadder LO:HI   with --chains R, R a multiple of K = HI-LO+1: chain r has nCol LO + r % K and\n"
               << "                       seed seed + r / K; prints a line per chain and the best one (not with --nCol;\n"
-              << "                       2 <= LO <= HI <= 256, HI above 64 runs the wide sweep)\n"
+              << "                       2 <= LO <= HI <= 2048, HI above 64 runs the wide sweep, above 256 the\n"
+              << "                       half-word sweep)\n"
               << "  --seed N             seed (default: time, which also srand()s glibc)\n"
               << "  --outDir D           output directory\n"
               << "  --device D           HIP device (default 0)\n"
@@ -193,7 +197,7 @@ int main(int argc, char** argv) {
                     if (colon == std::string::npos) throw 1;
                     ladderLo = (uint32_t)std::stoi(a.substr(0, colon));
                     ladderHi = (uint32_t)std::stoi(a.substr(colon + 1));
-                    if (ladderLo < 2 || ladderHi > 256 || ladderLo > ladderHi) throw 1;
+                    if (ladderLo < 2 || ladderHi > 2048 || ladderLo > ladderHi) throw 1;
                     break;
                 }
                 case 'S': seed = (uint32_t)std::stoi(optarg); break;
@@ -227,13 +231,13 @@ int main(int argc, char** argv) {
         mcmcgpu = true;
     }
     if (chains && (repetSet || gpus > 1 || !mcmcgpu || mcmccpu || greedyff || lubygpu || vffgpu ||
-                   chains > 1024 || nCol > 256)) {
-        std::cout << "--chains R batches --mcmcgpu alone: 1 <= R <= 1024, --nCol <= 256, no --repet, --gpus > 1 "
+                   chains > 1024 || nCol > 2048)) {
+        std::cout << "--chains R batches --mcmcgpu alone: 1 <= R <= 1024, --nCol <= 2048, no --repet, --gpus > 1 "
                      "or other colorer" << std::endl;
         return 255;
     }
     if (ladderLo && (!chains || nCol || chains % (ladderHi - ladderLo + 1))) {
-        std::cout << "--nColLadder LO:HI (2 <= LO <= HI <= 256) needs --chains R with R a multiple of HI - LO + 1, and no --nCol"
+        std::cout << "--nColLadder LO:HI (2 <= LO <= HI <= 2048) needs --chains R with R a multiple of HI - LO + 1, and no --nCol"
                   << std::endl;
         return 255;
     }
@@ -320,16 +324,24 @@ int main(int argc, char** argv) {
         params.maxRip = 250;
         params.tabooIteration = tabooIteration;
         params.tailcut = tailcut;
-        if (!ladderLo && params.nCol > 256) {
-            std::cout << "--chains needs nCol <= 256 (default nCol = " << params.nCol << ": give --nCol)" << std::endl;
+        if (!ladderLo && params.nCol > 2048) {
+            std::cout << "--chains needs nCol <= 2048 (default nCol = " << params.nCol << ": give --nCol)" << std::endl;
+            return 255;
+        }
+        const uint32_t top = ladderLo ? ladderHi : params.nCol;   // the batch's largest nCol
+        if (tailcutRepair && top > 256) {
+            std::cout << "--tailcutRepair with --chains needs nCol <= 256 (the half-word batch has no tail cut), got "
+                      << top << std::endl;
             return 255;
         }
         std::vector<mcmc_chain_spec> specs;
         for (uint32_t r = 0, K = ladderHi - ladderLo + 1; ladderLo && r < chains; r++)
             specs.push_back(mcmc_chain_spec{ladderLo + r % K, seed + r / K, params.epsilon, 0u});
         using Chains = ColoringMCMCChains<float, float>;
-        const bool wide = ladderLo ? ladderHi > 64 : params.nCol > 64;   // above 64 colours: the wide sweep
+        const bool wide = top > 64;   // above 64 colours: the wide sweep, above 256 the half-word one
         std::unique_ptr<Chains> bp(
+            top > 256 ? (ladderLo ? new Chains(Chains::Wide16{}, g, params, specs)
+                                  : new Chains(Chains::Wide16{}, g, GPURandGen.randStates, params, chains)) :
             wide ? (ladderLo ? new Chains(Chains::Wide{}, g, params, specs)
                              : new Chains(Chains::Wide{}, g, GPURandGen.randStates, params, chains))
                  : (ladderLo ? new Chains(g, params, specs) : new Chains(g, GPURandGen.randStates, params, chains)));
