@@ -377,7 +377,7 @@ public:
     ColoringMCMCChains(Wide, Graph<nodeW, edgeW>* inGraph_d, ColoringMCMCParams params, std::vector<mcmc_chain_spec> ladder)
         : graph(inGraph_d), seed(ladder.empty() ? 0u : ladder[0].seed), param(params), R((uint32_t)ladder.size()),
           specs(std::move(ladder)), wide(true) {}
-    // The half-word batch (mcmc_chains_create_wide16): per-chain nCol up to 2048, 16-bit colours; no setRepair.
+    // The half-word batch (mcmc_chains_create_wide16): per-chain nCol up to 2048, 16-bit colours.
     struct Wide16 {};
     ColoringMCMCChains(Wide16, Graph<nodeW, edgeW>* inGraph_d, GPURandHandle* randStates, ColoringMCMCParams params,
                        uint32_t chains)
@@ -389,8 +389,9 @@ public:
     ColoringMCMCChains& operator=(const ColoringMCMCChains&) = delete;
     ~ColoringMCMCChains() { mcmc_chains_destroy(ctx); }
 
-    // The batched tail cut after the loop (mcmc_chains_enable_repair): at most maxPasses passes per
-    // chain; 0 (the default) disables it. Takes effect at the next run().
+    // The batched tail cut after the loop (mcmc_chains_enable_repair; mcmc_chains_enable_repair16 for the
+    // half-word batch): at most maxPasses passes per chain; 0 (the default) disables it. Takes effect at
+    // the next run().
     void setRepair(uint32_t maxPasses) { repair = maxPasses; }
 
     void run() {
@@ -415,7 +416,7 @@ public:
         else
             MCMC_CHECK(mcmc_chains_create_ladder(graph->handle(), &p, specs.data(), R, &ctx));
         MCMC_CHECK(mcmc_chains_set_tailcut_repair(ctx, param.tailcutRepair));
-        if (repair) MCMC_CHECK(mcmc_chains_enable_repair(ctx, repair));
+        if (repair) MCMC_CHECK(wide16 ? mcmc_chains_enable_repair16(ctx, repair) : mcmc_chains_enable_repair(ctx, repair));
         std::vector<uint32_t> w((size_t)R * 31);
         for (uint32_t r = 0; r < R; r++) std::memcpy(&w[(size_t)r * 31], mcmc::glibc_global().w, 31 * sizeof(uint32_t));
         MCMC_CHECK(mcmc_chains_set_glibc_windows(ctx, w.data()));
@@ -549,7 +550,7 @@ private:
     std::vector<mcmc_chain_spec> specs;   // a ladder's; empty: uniform
     bool wide{false};                     // mcmc_chains_create_wide
     bool wide16{false};                   // mcmc_chains_create_wide16
-    uint32_t repair{0};                   // mcmc_chains_enable_repair's max_passes
+    uint32_t repair{0};                   // mcmc_chains_enable_repair's / _repair16's max_passes
     mcmc_chains* ctx{nullptr};
     std::vector<mcmc_run_stats> stats;
 };

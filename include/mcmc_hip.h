@@ -304,7 +304,8 @@ int mcmc_chains_create_wide(const mcmc_graph* g, const mcmc_params* p, const mcm
  * bit, the single run with its own (nCol, epsilon, seed). Class sizes: mcmc_chains_get_histograms_n
  * with cols >= the largest nCol (the device counts 512, 1024 or 2048 colours per chain; at most 65504
  * vertices per workgroup in packed 16-bit counters, exact). mcmc_chains_enable_repair(max_passes > 0)
- * on such a batch is MCMC_E_ARG: the batched tail cut reads byte colours. */
+ * on such a batch is MCMC_E_ARG: it reads byte colours. The batched tail cut of a half-word batch is
+ * mcmc_chains_enable_repair16. */
 int mcmc_chains_create_wide16(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_spec* specs /* may be NULL */,
                               uint32_t R, mcmc_chains** out);
 /* out[0] adjacency source of the sweep (0 CSR, 1 tiled layout), [1] device bytes of the batch's own
@@ -312,7 +313,7 @@ int mcmc_chains_create_wide16(const mcmc_graph* g, const mcmc_params* p, const m
  * (mcmc_chains_create_ladder, mcmc_chains_create_wide, _wide16), else 0, [6] mask words of the sweep: 0 for
  * the narrow kernels, 4 or 8 for the wide one, 16, 32 or 64 for the half-word one (whose workgroups
  * are 4, 4 and 2 waves: [4] counts them), [7] the tail-cut repair's time on the stream in
- * microseconds (hipEvent; 0 until mcmc_chains_enable_repair's repair ran). */
+ * microseconds (hipEvent; 0 until mcmc_chains_enable_repair's / _repair16's repair ran). */
 int mcmc_chains_get_info(mcmc_chains* c, uint64_t out[8]);
 /* windows[R][31]; default: every chain at srand(1) with no draws (mcmc_set_glibc_window's default).
  * mcmc_chains_get_glibc_windows returns them advanced by each chain's glibcDraws. */
@@ -334,8 +335,21 @@ int mcmc_chains_set_tailcut_repair(mcmc_chains* c, uint32_t max_passes);
  * flag words and lists and selects the sweeps that keep the flags; after a run has started it is
  * MCMC_E_ARG. max_passes = 0 disables it. Two calls because mcmc_chains_set_tailcut_repair's refusal
  * of max_passes > 0 is a documented behaviour that callers and tests rely on: the capability has an
- * entry point of its own, as mcmc_chains_create_wide has. */
+ * entry point of its own, as mcmc_chains_create_wide has. A half-word batch (mcmc_chains_create_wide16)
+ * is MCMC_E_ARG here, for the same reason: its repair is mcmc_chains_enable_repair16. */
 int mcmc_chains_enable_repair(mcmc_chains* c, uint32_t max_passes);
+/* The batched tail cut of a half-word batch (csrc/chains_tailcut16.h): mcmc_chains_enable_repair's
+ * contract -- stats, tailcutPasses, the fixed-point rule, info[7], the repaired colourings and
+ * histograms, "a run cut short by max_sweeps repairs nothing" -- for mcmc_chains_create_wide16's
+ * batches, nCol up to 2048: chain r ends, bit for bit, as the oracle's run with tailcutRepair and its
+ * own (nCol, epsilon, seed). Half-word batches only: on any other batch it is MCMC_E_ARG ("chains: ..."),
+ * and so it is after a run has started. max_passes = 0 disables it. The first call with max_passes > 0
+ * allocates, with G = ceil(R / 64) and up(x) = x rounded up to a multiple of 256,
+ *   up(16 n G) (the sweeps' flag words) + up(8 n G) (a pass's flag words) + up(4 n G) (lists)
+ *   + up(4 G) (list lengths) + up(2 * 64 * ncmax * G) (the colour order, uint16_t [64 G][ncmax], ncmax =
+ *   the batch's largest nCol) + up(4 * 64 G + 8 G) (counts and changed words, one block)
+ * bytes, else MCMC_E_NOMEM with the byte counts, and selects the half-word sweeps that keep the flags. */
+int mcmc_chains_enable_repair16(mcmc_chains* c, uint32_t max_passes);
 /* Every chain's run() loop; each stops at its own sweep. max_sweeps > 0: at most that many sweeps
  * (chains still running then report iter = sweeps, finalViol = ~0, as mcmc_run; a later call
  * continues). stats[R] (may be NULL): per chain, loopMs = the batch's device time (hipEvent). */

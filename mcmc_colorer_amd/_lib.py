@@ -75,6 +75,7 @@ SIGNATURES: dict[str, tuple] = {
     "mcmc_chains_get_glibc_windows": (c_int, [c_void_p, _u32p]),
     "mcmc_chains_set_tailcut_repair": (c_int, [c_void_p, c_uint32]),
     "mcmc_chains_enable_repair": (c_int, [c_void_p, c_uint32]),
+    "mcmc_chains_enable_repair16": (c_int, [c_void_p, c_uint32]),
     "mcmc_chains_run": (c_int, [c_void_p, c_uint32, c_void_p]),
     "mcmc_chains_get_coloring": (c_int, [c_void_p, c_uint32, _u32p]),
     "mcmc_chains_get_trajectory": (c_int, [c_void_p, c_uint32, _u64p, c_uint64, _u64p]),

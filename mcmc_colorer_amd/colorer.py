@@ -372,12 +372,16 @@ class ColoringMCMCChains:
     256 per chain, the occupancy masks in LDS; ``histograms()`` then has 256 columns.
     ``wide16=True`` (not with ``wide``) runs the half-word sweep, mcmc_chains_create_wide16: 2 <= nCol <=
     2048 per chain, 16-bit colours; ``histograms()`` then has as many columns as the largest nCol, and
-    ``repair > 0`` raises the library's error."""
+    ``repair > 0`` raises the library's error. ``repair16=N`` (here and in ``ladder``) is that batch's tail
+    cut, mcmc_chains_enable_repair16, with ``repair``'s meaning (not with ``repair``); without ``wide16`` it
+    raises the library's error."""
 
     def __init__(self, graph: Graph, params: ColoringMCMCParams, seed: int, chains: int, glibc=None, specs=None,
-                 wide: bool = False, repair: int = 0, wide16: bool = False):
+                 wide: bool = False, repair: int = 0, wide16: bool = False, repair16: int = 0):
         if wide and wide16:
             raise ValueError("wide and wide16 are mutually exclusive")
+        if repair and repair16:
+            raise ValueError("repair and repair16 are mutually exclusive")
         if params.nCol == 0 and specs is None:
             params = ColoringMCMCParams(**{**params.__dict__, "nCol": default_ncol(graph, params)})
         self.graph, self.param, self.seed, self.chains = graph, params, seed, int(chains)
@@ -400,6 +404,8 @@ class ColoringMCMCChains:
         check(lib().mcmc_chains_set_tailcut_repair(self._h, int(params.tailcutRepair)))
         if repair:
             check(lib().mcmc_chains_enable_repair(self._h, int(repair)))
+        if repair16:
+            check(lib().mcmc_chains_enable_repair16(self._h, int(repair16)))
         if glibc is None:
             glibc = GlibcRand(1)
         self.glibc = [glibc] * self.chains if isinstance(glibc, GlibcRand) else list(glibc)
@@ -407,14 +413,14 @@ class ColoringMCMCChains:
 
     @classmethod
     def ladder(cls, graph: Graph, params: ColoringMCMCParams, specs, glibc=None, wide: bool = False,
-               repair: int = 0, wide16: bool = False) -> "ColoringMCMCChains":
+               repair: int = 0, wide16: bool = False, repair16: int = 0) -> "ColoringMCMCChains":
         """One batch whose chain r has its own ``specs[r] = (nCol, epsilon, seed)`` (2 <= nCol <= 64, <= 256
         with ``wide=True``, <= 2048 with ``wide16=True``): mcmc_chains_create_ladder / _wide / _wide16. ``params``
         supplies maxRip, tabooIteration and tailcut; its nCol and epsilon are ignored. Chain r equals the
         single run with its own three values, bit for bit."""
         specs = list(specs)
         return cls(graph, params, specs[0][2] if specs else 0, len(specs), glibc=glibc, specs=specs, wide=wide,
-                   repair=repair, wide16=wide16)
+                   repair=repair, wide16=wide16, repair16=repair16)
 
     def run(self, max_sweeps: int = 0) -> list[MCMCRunStats]:
         w = np.ascontiguousarray(np.stack([g.window for g in self.glibc]), dtype=np.uint32)

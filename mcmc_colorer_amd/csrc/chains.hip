@@ -74,7 +74,8 @@
 //   (C16[buffer][group][v][64]). chains_sweep_wide16_kernel<TILED, MW> has MW = 16, 32 or 64 table words per
 //   chain, counts newly set bits with the returning ds_or so that a chain's Zv is one LDS word, and walks
 //   the CDF with cdf_walk.h per lane. The init and commit kernels are templates over the colour element;
-//   class sizes come from chains_hist16_kernel; the tail cut is refused for such a batch.
+//   class sizes come from chains_hist16_kernel; its tail cut is mcmc_chains_enable_repair16 (chains_tailcut16.h:
+//   half-word normalise, recount and repair kernels, the colour order in global memory, walked by a whole wave).
 // Tail cut (mcmc_chains_enable_repair, chains_tailcut.h): after the loop every chain that stopped with
 //   violators is repaired as the single run's corrected tail cut repairs it, 64 chains per row read; the
 //   sweeps' FLAGS instantiations keep the violator ballots its first pass needs.
@@ -590,6 +591,7 @@ __global__ __launch_bounds__(64 * kHistWaves) void chains_hist_kernel(ChainArgs 
 #include "chains_wide.h"
 #include "chains_wide16.h"
 #include "chains_tailcut.h"
+#include "chains_tailcut16.h"
 
 }  // namespace
 }  // namespace mcmc
@@ -671,19 +673,19 @@ namespace {
 template <bool FLAGS>
 void chains_launch_sweep(mcmc_chains* c, dim3 grid, uint32_t tn) {
     const ChainArgs& a = c->a;
-    if (c->esz == 2u) {   // the half-word batch: no FLAGS instantiations (mcmc_chains_enable_repair refuses it)
+    if (c->esz == 2u) {   // the half-word batch (FLAGS: mcmc_chains_enable_repair16)
         if (c->mw == 64u && c->tiled)
-            chains_sweep_wide16_kernel<true, 64><<<grid, 64 * wide16_waves(64), 0, c->stream>>>(a, c->t, tn);
+            chains_sweep_wide16_kernel<true, 64, FLAGS><<<grid, 64 * wide16_waves(64), 0, c->stream>>>(a, c->t, tn);
         else if (c->mw == 64u)
-            chains_sweep_wide16_kernel<false, 64><<<grid, 64 * wide16_waves(64), 0, c->stream>>>(a, c->t, tn);
+            chains_sweep_wide16_kernel<false, 64, FLAGS><<<grid, 64 * wide16_waves(64), 0, c->stream>>>(a, c->t, tn);
         else if (c->mw == 32u && c->tiled)
-            chains_sweep_wide16_kernel<true, 32><<<grid, 64 * wide16_waves(32), 0, c->stream>>>(a, c->t, tn);
+            chains_sweep_wide16_kernel<true, 32, FLAGS><<<grid, 64 * wide16_waves(32), 0, c->stream>>>(a, c->t, tn);
         else if (c->mw == 32u)
-            chains_sweep_wide16_kernel<false, 32><<<grid, 64 * wide16_waves(32), 0, c->stream>>>(a, c->t, tn);
+            chains_sweep_wide16_kernel<false, 32, FLAGS><<<grid, 64 * wide16_waves(32), 0, c->stream>>>(a, c->t, tn);
         else if (c->tiled)
-            chains_sweep_wide16_kernel<true, 16><<<grid, 64 * wide16_waves(16), 0, c->stream>>>(a, c->t, tn);
+            chains_sweep_wide16_kernel<true, 16, FLAGS><<<grid, 64 * wide16_waves(16), 0, c->stream>>>(a, c->t, tn);
         else
-            chains_sweep_wide16_kernel<false, 16><<<grid, 64 * wide16_waves(16), 0, c->stream>>>(a, c->t, tn);
+            chains_sweep_wide16_kernel<false, 16, FLAGS><<<grid, 64 * wide16_waves(16), 0, c->stream>>>(a, c->t, tn);
     } else if (c->mw == 8u && c->tiled)
         chains_sweep_wide_kernel<true, 8, FLAGS><<<grid, 64 * kSweepWaves, 0, c->stream>>>(a, c->t, tn);
     else if (c->mw == 8u)
@@ -730,6 +732,25 @@ int chains_histograms(mcmc_chains* c) {
     return MCMC_OK;
 }
 
+// a pass's repair kernel of a half-word batch: the batch's table words, CSR or tiled rows
+void chains_launch_repair16(mcmc_chains* c, const TailMasks& act) {
+    const ChainArgs& a = c->a;
+    const TailArgs& ta = c->ta;
+    const uint32_t G = a.G, nc = c->maxncol;
+    if (c->mw == 64u && c->tiled)
+        chains_tail_repair16_kernel<true, 64><<<G * kTail16Subs, 64 * kTail16Waves, 0, c->stream>>>(a, ta, act, nc);
+    else if (c->mw == 64u)
+        chains_tail_repair16_kernel<false, 64><<<G * kTail16Subs, 64 * kTail16Waves, 0, c->stream>>>(a, ta, act, nc);
+    else if (c->mw == 32u && c->tiled)
+        chains_tail_repair16_kernel<true, 32><<<G * kTail16Subs, 64 * kTail16Waves, 0, c->stream>>>(a, ta, act, nc);
+    else if (c->mw == 32u)
+        chains_tail_repair16_kernel<false, 32><<<G * kTail16Subs, 64 * kTail16Waves, 0, c->stream>>>(a, ta, act, nc);
+    else if (c->tiled)
+        chains_tail_repair16_kernel<true, 16><<<G * kTail16Subs, 64 * kTail16Waves, 0, c->stream>>>(a, ta, act, nc);
+    else
+        chains_tail_repair16_kernel<false, 16><<<G * kTail16Subs, 64 * kTail16Waves, 0, c->stream>>>(a, ta, act, nc);
+}
+
 // The corrected tail cut of every chain that stopped with violators (chains_tailcut.h), after the run
 // in which the last chain stopped. c->st is the state at loop exit.
 int chains_repair(mcmc_chains* c) {
@@ -752,15 +773,21 @@ int chains_repair(mcmc_chains* c) {
     }
     MCMC_HIP_TRY(hipEventRecord(c->ev0, c->stream));
     const dim3 ngrid((uint32_t)(((uint64_t)n * 16u + 255u) / 256u), G);
-    chains_tail_normalise_kernel<<<ngrid, 256, 0, c->stream>>>(a, ta, buf1, par1);
+    if (c->esz == 2u)   // the same grid: n x 16 words of 8 bytes
+        chains_tail_normalise16_kernel<<<ngrid, 256, 0, c->stream>>>(a, ta, buf1, par1);
+    else
+        chains_tail_normalise_kernel<<<ngrid, 256, 0, c->stream>>>(a, ta, buf1, par1);
     MCMC_HIP_TRY(hipGetLastError());
     for (auto& h : c->st) h.buf = 0u;
     MCMC_HIP_TRY(hipMemcpyAsync(a.st, c->st.data(), sizeof(ChainState) * R, hipMemcpyHostToDevice, c->stream));
     MCMC_HIP_TRY(hipStreamSynchronize(c->stream));   // c->st may change under the caller from here on
-    if (any) {
+    if (any && !(c->esz == 2u && a.z == 0u)) {   // a half-word batch reads no table for the identity order
         // colorIdx: the identity (:131-132); with z > 0 sorted by ascending class size (:272-278), by
         // std::sort with the reference's comparator, so ties resolve as the reference's do
-        std::vector<uint8_t> cidx((size_t)G * kLanes * 256u, 0);
+        // bytes [G * 64][256]; a half-word batch: uint16_t [G * 64][ncmax] (chains_tailcut16.h)
+        const uint32_t ncmax = c->maxncol;
+        std::vector<uint8_t> cidx(c->esz == 2u ? 2 * (size_t)G * ncmax * kLanes : (size_t)G * kLanes * 256u, 0);
+        uint16_t* cidx16 = reinterpret_cast<uint16_t*>(cidx.data());
         if (a.z > 0u) {
             int rc = chains_histograms(c);
             if (rc) return rc;
@@ -776,16 +803,24 @@ int chains_repair(mcmc_chains* c) {
                 std::vector<size_t> histBins(c->hist.begin() + (size_t)r * hc, c->hist.begin() + (size_t)r * hc + k);
                 std::sort(colorIdx.begin(), colorIdx.end(), [&](int i, int j) { return histBins[i] < histBins[j]; });
             }
-            for (uint32_t i = 0; i < k; i++) cidx[(size_t)r * 256u + i] = (uint8_t)colorIdx[i];
+            for (uint32_t i = 0; i < k; i++) {
+                if (c->esz == 2u)
+                    cidx16[(size_t)r * ncmax + i] = (uint16_t)colorIdx[i];
+                else
+                    cidx[(size_t)r * 256u + i] = (uint8_t)colorIdx[i];
+            }
         }
         MCMC_HIP_TRY(hipMemcpyAsync(ta.cidx, cidx.data(), cidx.size(), hipMemcpyHostToDevice, c->stream));
         MCMC_HIP_TRY(hipStreamSynchronize(c->stream));   // cidx leaves scope
     }
-    const dim3 cgrid(chains_grid_x(a), G);
+    const dim3 cgrid(chains_grid_x(a, c->sweep_waves()), G);
     const uint32_t RP = G * kLanes;
     for (uint32_t pass = 1; any && pass <= c->repair_max; pass++) {
         chains_tail_list_kernel<<<G, kTailListThreads, 0, c->stream>>>(a, ta, act);
-        if (c->tiled && c->maxncol > 128u)
+        if (c->esz == 2u) {   // its workgroups OR their changed bits into the groups' words
+            MCMC_HIP_TRY(hipMemsetAsync(ta.chg, 0, 8 * (size_t)G, c->stream));
+            chains_launch_repair16(c, act);
+        } else if (c->tiled && c->maxncol > 128u)
             chains_tail_repair_kernel<true, 8><<<G, 64 * kTailWaves, 0, c->stream>>>(a, ta, act);
         else if (c->tiled)
             chains_tail_repair_kernel<true, 4><<<G, 64 * kTailWaves, 0, c->stream>>>(a, ta, act);
@@ -793,7 +828,11 @@ int chains_repair(mcmc_chains* c) {
             chains_tail_repair_kernel<false, 8><<<G, 64 * kTailWaves, 0, c->stream>>>(a, ta, act);
         else
             chains_tail_repair_kernel<false, 4><<<G, 64 * kTailWaves, 0, c->stream>>>(a, ta, act);
-        if (c->tiled)
+        if (c->esz == 2u && c->tiled)
+            chains_tail_count16_kernel<true><<<cgrid, 64 * c->sweep_waves(), 0, c->stream>>>(a, ta, act);
+        else if (c->esz == 2u)
+            chains_tail_count16_kernel<false><<<cgrid, 64 * c->sweep_waves(), 0, c->stream>>>(a, ta, act);
+        else if (c->tiled)
             chains_tail_count_kernel<true><<<cgrid, 64 * kSweepWaves, 0, c->stream>>>(a, ta, act);
         else
             chains_tail_count_kernel<false><<<cgrid, 64 * kSweepWaves, 0, c->stream>>>(a, ta, act);
@@ -984,6 +1023,47 @@ int chains_create(const mcmc_graph* g, const mcmc_params* p, const mcmc_chain_sp
 
 }  // namespace
 
+namespace {
+
+// mcmc_chains_enable_repair / _repair16 after their checks: the pass cap and, once, the flag words, the
+// lists and the colour-order table (bytes [G * 64][256]; a half-word batch: uint16_t [G * 64][largest nCol])
+int chains_enable_repair(mcmc_chains* c, uint32_t max_passes) {
+    MCMC_HIP_TRY(hipSetDevice(c->device));
+    c->repair_max = max_passes;
+    if (!max_passes || c->rmem) return MCMC_OK;
+    const ChainArgs& a = c->a;
+    const size_t n = a.n, G = a.G, RP = G * kLanes;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_vfl = up(16 * n * G), b_fl = up(8 * n * G), b_list = up(4 * n * G), b_len = up(4 * G),
+                 b_cidx = up(c->esz == 2u ? 2 * kLanes * (size_t)c->maxncol * G : 256 * RP), b_cnt = up(4 * RP + 8 * G);
+    const size_t need = b_vfl + b_fl + b_list + b_len + b_cidx + b_cnt;
+    hipError_t e = hipMalloc(&c->rmem, need);
+    if (e == hipSuccess) e = hipMemset(c->rmem, 0, need);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&c->rpin), 4 * RP + 8 * G);
+    if (e != hipSuccess) {
+        if (c->rmem) (void)hipFree(c->rmem);
+        c->rmem = nullptr;
+        c->repair_max = 0;
+        return fail(e == hipErrorOutOfMemory ? MCMC_E_NOMEM : MCMC_E_HIP,
+                    std::string("chains: tail-cut repair needs ") + std::to_string(need) + " bytes (sweep flags " +
+                        std::to_string(b_vfl) + ", pass flags " + std::to_string(b_fl) + ", lists " + std::to_string(b_list) +
+                        ", colour order " + std::to_string(b_cidx) + "): " + hipGetErrorString(e));
+    }
+    uint8_t* at = static_cast<uint8_t*>(c->rmem);
+    auto take = [&](size_t b) { uint8_t* q = at; at += b; return q; };
+    c->a.vfl = reinterpret_cast<uint64_t*>(take(b_vfl));
+    c->ta.fl = reinterpret_cast<uint64_t*>(take(b_fl));
+    c->ta.list = reinterpret_cast<uint32_t*>(take(b_list));
+    c->ta.listlen = reinterpret_cast<uint32_t*>(take(b_len));
+    c->ta.cidx = take(b_cidx);
+    c->ta.cnt = reinterpret_cast<uint32_t*>(take(b_cnt));
+    c->ta.chg = reinterpret_cast<uint64_t*>(c->ta.cnt + RP);   // 4 RP is a multiple of 8
+    c->rbytes = need;
+    return MCMC_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int mcmc_chains_create(const mcmc_graph* g, const mcmc_params* p, uint32_t R, mcmc_chains** out) {
@@ -1070,38 +1150,18 @@ int mcmc_chains_enable_repair(mcmc_chains* c, uint32_t max_passes) {
     if (!c) return fail(MCMC_E_ARG, "NULL context");
     if (c->t != 0u) return fail(MCMC_E_ARG, "chains: mcmc_chains_enable_repair after a run has started (the sweeps so far kept no flags)");
     if (max_passes && c->esz == 2u)
-        return fail(MCMC_E_ARG, "chains: the batched tail cut reads byte colours: a half-word batch "
-                                "(mcmc_chains_create_wide16) has no repair");
-    MCMC_HIP_TRY(hipSetDevice(c->device));
-    c->repair_max = max_passes;
-    if (!max_passes || c->rmem) return MCMC_OK;
-    const ChainArgs& a = c->a;
-    const size_t n = a.n, G = a.G, RP = G * kLanes;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_vfl = up(16 * n * G), b_fl = up(8 * n * G), b_list = up(4 * n * G), b_len = up(4 * G),
-                 b_cidx = up(256 * RP), b_cnt = up(4 * RP + 8 * G);
-    const size_t need = b_vfl + b_fl + b_list + b_len + b_cidx + b_cnt;
-    hipError_t e = hipMalloc(&c->rmem, need);
-    if (e == hipSuccess) e = hipMemset(c->rmem, 0, need);
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&c->rpin), 4 * RP + 8 * G);
-    if (e != hipSuccess) {
-        if (c->rmem) (void)hipFree(c->rmem);
-        c->rmem = nullptr;
-        c->repair_max = 0;
-        return fail(e == hipErrorOutOfMemory ? MCMC_E_NOMEM : MCMC_E_HIP,
-                    std::string("chains: tail-cut repair needs ") + std::to_string(need) + " bytes: " + hipGetErrorString(e));
-    }
-    uint8_t* at = static_cast<uint8_t*>(c->rmem);
-    auto take = [&](size_t b) { uint8_t* q = at; at += b; return q; };
-    c->a.vfl = reinterpret_cast<uint64_t*>(take(b_vfl));
-    c->ta.fl = reinterpret_cast<uint64_t*>(take(b_fl));
-    c->ta.list = reinterpret_cast<uint32_t*>(take(b_list));
-    c->ta.listlen = reinterpret_cast<uint32_t*>(take(b_len));
-    c->ta.cidx = take(b_cidx);
-    c->ta.cnt = reinterpret_cast<uint32_t*>(take(b_cnt));
-    c->ta.chg = reinterpret_cast<uint64_t*>(c->ta.cnt + RP);   // 4 RP is a multiple of 8
-    c->rbytes = need;
-    return MCMC_OK;
+        return fail(MCMC_E_ARG, "chains: mcmc_chains_enable_repair reads byte colours: a half-word batch "
+                                "(mcmc_chains_create_wide16) is repaired by mcmc_chains_enable_repair16");
+    return chains_enable_repair(c, max_passes);
+}
+
+int mcmc_chains_enable_repair16(mcmc_chains* c, uint32_t max_passes) {
+    if (!c) return fail(MCMC_E_ARG, "NULL context");
+    if (c->esz != 2u)
+        return fail(MCMC_E_ARG, "chains: mcmc_chains_enable_repair16 reads 16-bit colours: a batch other than "
+                                "mcmc_chains_create_wide16's is repaired by mcmc_chains_enable_repair");
+    if (c->t != 0u) return fail(MCMC_E_ARG, "chains: mcmc_chains_enable_repair16 after a run has started (the sweeps so far kept no flags)");
+    return chains_enable_repair(c, max_passes);
 }
 
 int mcmc_chains_get_glibc_windows(mcmc_chains* c, uint32_t* windows) {

@@ -37,7 +37,9 @@
 //   workgroup counts 16384 / hc chains (hc = 32 MW columns: 32, 16 or 8 chains) of a vertex chunk in a
 //   32 KB table of packed 16-bit counters, at most 65504 vertices so that no counter carries, then
 //   adds its nonzero cells to the global rows of hc words.
-// Not here: the batched tail cut (chains_tailcut.h reads byte colours): no FLAGS instantiations.
+// FLAGS (mcmc_chains_enable_repair16, chains_tailcut16.h): as in chains_sweep_kernel, lane 0 keeps the
+//   ballot of `viol` per (group, v) in a.vfl[t & 1], merged under the live mask. The FLAGS = false code
+//   objects are the ones below, unchanged.
 //
 // Resources (hipcc -O3 -ffp-contract=off, gfx950, -Rpass-analysis=kernel-resource-usage):
 //   chains_sweep_wide16_kernel  <CSR, 16>    <CSR, 32>    <CSR, 64>    <tiled, 16>  <tiled, 32>  <tiled, 64>
@@ -45,6 +47,7 @@
 //   SGPRs                       99           99           99           106          106          106
 //   scratch (bytes / lane)      0            0            0            0            0            0
 //   LDS (bytes)                 17664        34048        33536        17664        34048        33536
+//   FLAGS = true: the same VGPRs, scratch and LDS; SGPRs 105 (CSR) and 106 (tiled).
 #pragma once
 
 // a wave-private LDS column seen as the `mask` of cdf_walk.h's walk_mask: element w is word w
@@ -102,7 +105,8 @@ __device__ __forceinline__ void drain_chunk_wide16(const uint64_t* __restrict__ 
 
 // TILED as in chains_sweep_kernel. MW: 32-bit words of a chain's occupancy column (16: every nCol <= 512,
 // 32: <= 1024, 64: <= 2048). nCol, epsilon, hi, fr, pf and the walk's end are per lane (a.ncolw, a.epsr).
-template <bool TILED, int MW>
+// FLAGS as in chains_sweep_kernel.
+template <bool TILED, int MW, bool FLAGS>
 __global__ __launch_bounds__(64 * wide16_waves(MW)) void chains_sweep_wide16_kernel(ChainArgs a, uint32_t t, uint32_t tn) {
     constexpr uint32_t kWaves = (uint32_t)wide16_waves(MW);
     if (*a.ndone >= a.R) return;   // every chain stopped (workgroup-uniform)
@@ -234,6 +238,11 @@ __global__ __launch_bounds__(64 * wide16_waves(MW)) void chains_sweep_wide16_ker
                                                     __HIP_MEMORY_SCOPE_WAVEFRONT);
             const bool viol = (ownw >> (c & 31u)) & 1u;
             nviol += (live && viol) ? 1u : 0u;
+            if constexpr (FLAGS) {
+                const uint64_t fb = __ballot(viol);
+                uint64_t* fw = a.vfl + ((size_t)(t & 1u) * a.G + g) * n + v;
+                if (lane == 0u) *fw = (*fw & ~livemask) | (fb & livemask);
+            }
             uint32_t tb = tab ? tab[(size_t)v * kLanes + lane] : 0u;
             uint32_t newc = c;
             bool ovf = false;

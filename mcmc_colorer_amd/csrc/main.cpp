@@ -12,8 +12,9 @@
 //   --chains R: with --mcmcgpu, seeds seed .. seed + R - 1 as one batch (csrc/chains.hip), each chain on
 //   its own copy of the glibc stream; writes the files --repet R names. nCol (from --nCol, the ladder's
 //   HI, or the reference's default maxDeg / numColRatio) in 257..2048 runs the half-word batch
-//   (mcmc_chains_create_wide16; not with --tailcutRepair), in 65..256 the wide batch
-//   (mcmc_chains_create_wide), nCol <= 64 the narrow one
+//   (mcmc_chains_create_wide16), in 65..256 the wide batch (mcmc_chains_create_wide), nCol <= 64 the
+//   narrow one; with --tailcutRepair the batch runs its tail cut after the loop (mcmc_chains_enable_repair,
+//   mcmc_chains_enable_repair16 for the half-word batch)
 //   --nColLadder LO:HI: with --chains R (a multiple of K = HI - LO + 1), chain r has nCol LO + r % K and
 //   seed seed + r / K (one batch, the ladder sweep); one summary line per chain and a `best:` line
 // Outputs <outDir>/<graphName>-MCMC_GPU-<i>.log and -colors.txt per repetition.
@@ -129,9 +130,9 @@ void help(const char* argv0) {
               << "  --tailcutRepair      then repair the remaining conflicts (corrected tail cut, <= 1000 passes)\n"
               << "  --repet N            repetitions, seeds seed+i (default 1)\n"
               << "  --chains R           --mcmcgpu: seeds seed .. seed+R-1 as ONE batch, a wave lane per chain\n"
-              << "                       (nCol <= 2048: above 64 the wide sweep, above 256 the half-word sweep, which\n"
-              << "                       has no --tailcutRepair; R <= 1024; each chain its own glibc stream; not with\n"
-              << "                       --repet / --gpus)\n"
+              << "                       (nCol <= 2048: above 64 the wide sweep, above 256 the half-word sweep;\n"
+              << "                       --tailcutRepair repairs every chain of any of them after the loop; R <= 1024;\n"
+              << "                       each chain its own glibc stream; not with --repet / --gpus)\n"
               << "  --nColLadder LO:HI   with --chains R, R a multiple of K = HI-LO+1: chain r has nCol LO + r % K and\n"
               << "                       seed seed + r / K; prints a line per chain and the best one (not with --nCol;\n"
               << "                       2 <= LO <= HI <= 2048, HI above 64 runs the wide sweep, above 256 the\n"
@@ -329,11 +330,6 @@ int main(int argc, char** argv) {
             return 255;
         }
         const uint32_t top = ladderLo ? ladderHi : params.nCol;   // the batch's largest nCol
-        if (tailcutRepair && top > 256) {
-            std::cout << "--tailcutRepair with --chains needs nCol <= 256 (the half-word batch has no tail cut), got "
-                      << top << std::endl;
-            return 255;
-        }
         std::vector<mcmc_chain_spec> specs;
         for (uint32_t r = 0, K = ladderHi - ladderLo + 1; ladderLo && r < chains; r++)
             specs.push_back(mcmc_chain_spec{ladderLo + r % K, seed + r / K, params.epsilon, 0u});
